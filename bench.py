@@ -40,6 +40,19 @@ does less work than it counts.  K steps are timed after W warmup steps, brackete
 and a device synchronize on both sides; value = answered questions per second over all
 ranks (max elapsed over ranks).  Weights are random-init (no checkpoints offline); data
 is synthetic.
+
+A plain run does only that: set up, W warmup steps, K timed steps, the result line.
+``--full`` adds the secondary measurement after the timed steps: the same pipeline under
+the closed-loop load for ``--also-stream`` steps, reported as ``stream_load``.
+
+``--dump-outputs DIR`` puts the last timed step's questions through the question
+pipeline's stages once more, last of all, at the step's batch shapes, and writes what the
+stages return as DIR/<name>.npy (``_replay_outputs``: question embeddings, kNN
+similarities, and the token ids and log-probabilities of the whole batch's greedy
+completions over the re-ranked, templated prompts).  The inputs are a function of the
+arguments alone (seeded weights, questions, corpus and pages by index), and unlike the
+step's own records the replay does not depend on thread timing, so two runs and two builds
+can be compared output for output.
 """
 from __future__ import annotations
 
@@ -347,9 +360,19 @@ def main():
     ap.add_argument("--timeout", type=float, default=900.0)
     ap.add_argument("--prefill-chunk", type=int, default=16384,
                     help="engine max-prefill-tokens per step (chunked prefill)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run the secondary measurements (today: the "
+                         "closed-loop window of --also-stream); a plain run only sets up, warms up, times --steps "
+                         "steps and prints the result line")
     ap.add_argument("--also-stream", type=int, default=3,
-                    help="burst load: afterwards time this many steps' worth of questions under the closed-loop "
-                         "load too and report it as stream_load (0: skip)")
+                    help="with --full, burst load: afterwards time this many steps' worth of questions under the "
+                         "closed-loop load too and report it as stream_load (0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rag: last of all put the last timed step's questions through the question pipeline's "
+                         "stages once more (embed, top-k search, re-rank, prompt template, the whole batch as one "
+                         "greedy generate of --max-tokens) and write DIR/question_embeddings.npy, "
+                         "DIR/knn_similarity.npy, DIR/completion_token_ids.npy and DIR/completion_logprobs.npy "
+                         "(float32)")
     ap.add_argument("--load", choices=("stream", "burst"), default="burst",
                     help="stream: closed loop, --batch questions in flight per GPU, a new question as each "
                          "answer arrives, a step = --batch answers; burst: --batch questions at the start of "
@@ -368,6 +391,10 @@ def main():
                     help="embed: agent replicas per GPU (resources.parallelism); > 1 runs each as its own "
                          "agent-pod process sharing the GPU")
     args = ap.parse_args()
+    if args.dump_outputs and args.config != "rag":
+        ap.error("--dump-outputs is implemented for --config rag (the headline) only")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     try:
         # byte-compile the package up front (~0.3 s cold): modules imported lazily by
         # agents / codecs must not compile inside the timed window on a fresh checkout
@@ -520,10 +547,14 @@ def main():
         k = balanced_key(f"{rank}-{seq[0]}", g % q_parts, q_parts)
         seq[0] += 1
         sent[k] = time.time()
+        if asked is not None:
+            asked.append(corpus[(g * 13) % len(corpus)])
         prod.write(_rec(k, corpus[(g * 13) % len(corpus)]))
         return k
 
     sent = {}
+    # --dump-outputs: the questions of the running step / window in sending order
+    asked = [] if args.dump_outputs else None
     phases = []
     stage_trace = []
 
@@ -560,6 +591,8 @@ def main():
 
     def run_step():
         step = steps_done[0]
+        if asked is not None and args.load == "burst":
+            asked.clear()
         t0 = time.time()
         if _composite.STAGE_TRACE is not None:
             threading.Thread(target=cpu_window, args=(cpu_front, 0.6), daemon=True, name="cpu-window").start()
@@ -628,6 +661,8 @@ def main():
         crawled pages of the k_steps steps are published as each batch of window
         questions starts and must be indexed before the window closes."""
         first = steps_done[0]
+        if asked is not None:
+            asked.clear()
         quota = k_steps * args.batch
         window = set()
         lats = []
@@ -705,15 +740,25 @@ def main():
         if c is not None and hasattr(c, "get_info"):
             info = c.get_info()
             assign[info["topic"]] = info.get("assignment")
+    # --dump-outputs: the last timed step's questions (stream: the window's last --batch)
+    last_asked = list(asked[-args.batch:]) if asked is not None else None
     stream_res = None
-    if args.load == "burst" and args.also_stream > 0:
+    if args.full and args.load == "burst" and args.also_stream > 0:
         # the same pipeline under the closed-loop load, reported beside the burst number
         barrier()
         ts0 = time.time()
         s_lats = run_window(args.also_stream)
         barrier()
         stream_res = {"elapsed": time.time() - ts0, "lats": s_lats}
+    # what the result line reports of the engine, read before the replay adds its requests
+    engine_report = {"engine_rank0": dict(stats, exec_ms=dict(zip(("upload", "enqueue", "download", "wait"),
+                                                                  (round(x, 1) for x in llm.exec.timings())))),
+                     "prompt_len_pcts_rank0": _pcts(list(llm.prompt_lens)),
+                     "prefill_step_tokens_rank0": list(llm.prefill_step_tokens)[-40:]}
+    # the replay comes last: nothing that is measured runs after it
+    dump = _replay_outputs(last_asked, files["pipeline.yaml"], emb, store, llm) if last_asked is not None else None
     mine = {"elapsed": elapsed, "lats": my_lats, "chunks": chunks, "assign": assign, "stream": stream_res,
+            "dump": dump,
             "prefill_tokens": stats.get("prefill_tokens", 0), "requests": stats.get("requests", 0),
             "prompt_tokens": stats.get("prompt_tokens", 0),
             "phases": phases, "stage_trace": stage_trace, "gc": {"pause_ms": round(gc_t["ms"], 1), "collections_by_gen": gc_t["n"]},
@@ -739,6 +784,8 @@ def main():
     total = args.batch * args.steps * world
     value = total / elapsed
     if rank == 0:
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, [g["dump"] for g in gathered])
         print(json.dumps({
             "metric": METRIC,
             "value": round(value, 3), "unit": "records/s", "n_gpus": world, "steps": args.steps,
@@ -767,11 +814,10 @@ def main():
             "knn_stats_rank0": gathered[0]["knn_stats"],
             "partitions_per_rank": [g["assign"] for g in gathered],
             "setup_s": round(setup_s, 1),
-            "engine_rank0": dict(stats, exec_ms=dict(zip(("upload", "enqueue", "download", "wait"),
-                                                         (round(x, 1) for x in llm.exec.timings())))),
+            "engine_rank0": engine_report["engine_rank0"],
             "stream_load": _stream_summary(gathered, args, world),
-            "prompt_len_pcts_rank0": _pcts(list(llm.prompt_lens)),
-            "prefill_step_tokens_rank0": list(llm.prefill_step_tokens)[-40:],
+            "prompt_len_pcts_rank0": engine_report["prompt_len_pcts_rank0"],
+            "prefill_step_tokens_rank0": engine_report["prefill_step_tokens_rank0"],
         }), flush=True)
     barrier()
     if crawler_host is not None:
@@ -836,6 +882,82 @@ def _other_config(args, rank: int, world: int, local: int) -> None:
     embed.run(args, rank, world, barrier, bcast, gpu_init)
     if ctrl is not None:
         dist.destroy_process_group()
+
+
+def _replay_outputs(questions, pipeline_yaml: str, emb, store, llm):
+    """--dump-outputs: the last timed step's B questions once more through the stages of
+    the question pipeline, configured from the pipeline's own YAML, on the engines the
+    timed steps ran on, as float32 arrays with one row per question in sending order:
+
+      question_embeddings   [B, dim]  compute-ai-embeddings, in the agent's batch-size
+      knn_similarity        [B, 20]   query-vector-db: cosine similarity of the top-k rows
+                                      of this rank's shard (with their vectors), best first
+      completion_token_ids  [B, T]    re-rank (MMR) of those rows, the chat step's message
+      completion_logprobs   [B, T]    templates rendered with the re-ranked documents, then
+                                      all B prompts as ONE generate() call of T = max-tokens
+                                      tokens: token ids and their log-probabilities
+
+    So the batched prefill (chunked, with prefix KV reuse among the B prompts), the batched
+    decode GEMMs, paged attention and the sampler run at the timed step's shapes.
+
+    The step's own records cannot serve: which documents a question retrieves depends on
+    how far the same step's crawled pages were indexed when it was searched, and its
+    completion is sampled at temperature 1 with a seed handed out in arrival order -- two
+    runs of one build differ in ~1 % of the prompts and in nearly every answer token.  The
+    replay removes what depends on thread timing and nothing else: it runs last, with every
+    page indexed and the pipeline idle; the completions are greedy; the engine's thread is
+    stopped while the B requests are queued and the steps are driven from here, so every
+    run schedules the same batches; and the prefix cache starts empty, so the prefix KV the
+    prompts reuse is captured from these prompts, not from whichever timed request came
+    first."""
+    import numpy as np
+    import yaml
+    from langstream_amd.agents.genai.mustache import compile_template
+    from langstream_amd.agents.genai.services import ChatMessage, llama3_chat_prompt
+    from langstream_amd.agents.rerank import mmr
+    from langstream_amd.engine.llm_engine import SamplingParams
+    steps = {a["type"]: a.get("configuration") or {} for a in yaml.safe_load(pipeline_yaml)["pipeline"]}
+    embed_cfg, rerank_cfg, chat_cfg = steps["compute-ai-embeddings"], steps["re-rank"], steps["ai-chat-completions"]
+    top_k = int(json.loads(steps["query-vector-db"]["query"].replace("?", "null"))["top-k"])
+    templates = [(m.get("role", "user"), compile_template(m.get("content") or "")) for m in chat_cfg["messages"]]
+    questions = list(questions)
+    bs = int(embed_cfg["batch-size"])
+    vec = np.concatenate([np.asarray(emb.embed(questions[i:i + bs]), dtype=np.float32)   # blocking, host rows
+                          for i in range(0, len(questions), bs)])
+    sims = np.zeros((len(questions), top_k), dtype=np.float32)
+    prompts = []
+    for i in range(0, len(questions), bs):
+        for q, hits in zip(questions[i:i + bs], store.search(vec[i:i + bs], k=top_k, with_vectors=True)):
+            sims[len(prompts), :len(hits)] = [h["similarity"] for h in hits]
+            docs = mmr(hits, [str(h["text"]) for h in hits],
+                       np.asarray([h["vector"] for h in hits], dtype=np.float32).reshape(len(hits), -1), q,
+                       int(rerank_cfg["max"]), float(rerank_cfg["lambda"]), float(rerank_cfg["k1"]), float(rerank_cfg["b"]))
+            ctx = {"value": {"question": q, "related_documents": docs}}
+            prompts.append(llm.tok.encode(llama3_chat_prompt([ChatMessage(role, t.render(ctx)) for role, t in templates])))
+    n_tok = int(chat_cfg["max-tokens"])
+    greedy = SamplingParams(max_tokens=n_tok, temperature=0.0, ignore_eos=True)
+    llm.stop()                      # no step runs while the requests are queued; generate() then steps inline
+    try:
+        if llm.prefix is not None:
+            llm.prefix.clear()
+        reqs = llm.generate(prompts, greedy)
+    finally:
+        llm.start()
+    toks = np.full((len(reqs), n_tok), -1.0, dtype=np.float32)
+    lps = np.zeros((len(reqs), n_tok), dtype=np.float32)
+    for i, r in enumerate(reqs):
+        toks[i, :len(r.output_ids)] = r.output_ids[:n_tok]
+        lps[i, :len(r.output_logprobs)] = r.output_logprobs[:n_tok]
+    return {"question_embeddings": vec, "knn_similarity": sims, "completion_token_ids": toks, "completion_logprobs": lps}
+
+
+def _dump_outputs(dirname: str, per_rank) -> None:
+    """Write the ranks' replayed arrays (``_replay_outputs``), rank 0's rows first, as
+    DIR/<name>.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name in per_rank[0]:
+        np.save(os.path.join(dirname, name + ".npy"), np.concatenate([d[name] for d in per_rank]))
 
 
 def _rec(key, value):

@@ -39,6 +39,46 @@ def _run(args, tmp_path, timeout=600):
     return json.loads(line[0])
 
 
+def test_bench_plain_run_is_lean_full_adds_stream_window_and_outputs_dump(tmp_path):
+    """A plain run times only its steps (no closed-loop window: stream_load is null; one
+    latency sample per question of exactly --steps steps); --full adds the window.
+    --dump-outputs replays the last timed step's questions through the question pipeline's
+    stages (embed, top-20 search, re-rank, prompt template, one greedy generate of the
+    whole batch) and writes float32 arrays, one row per question in sending order; the
+    inputs depend on the arguments alone and the replay does not depend on timing, so two
+    runs with crawl and ingest running write the same numbers (fp32 engines on CPU: 1e-5,
+    token ids equal)."""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4", "--max-tokens", "4", "--corpus", "1000",
+            "--docs", "2"]
+    a = _run([*args, "--dump-outputs", str(tmp_path / "a")], tmp_path)
+    c = _run([*args, "--dump-outputs", str(tmp_path / "c")], tmp_path)
+    b = _run([*args, "--full", "--also-stream", "1"], tmp_path)
+    assert a["stream_load"] is None and a["steps"] == 2 and a["latency_samples"] == 2 * 4
+    assert b["stream_load"]["steps"] == 1 and b["stream_load"]["value"] > 0 and b["steps"] == 2
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert a[k] == b[k] == c[k]
+    # the replay's 4 requests are not in what the line reports of the engine
+    assert a["engine_rank0"]["requests"] == 2 * 4 and a["prompt_len_pcts_rank0"] is not None
+    shapes = {"question_embeddings": (4, 128), "knn_similarity": (4, 20), "completion_token_ids": (4, 4),
+              "completion_logprobs": (4, 4)}
+    for d in ("a", "c"):
+        assert sorted(os.listdir(tmp_path / d)) == sorted(n + ".npy" for n in shapes)
+    for name, shape in shapes.items():
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "c" / f"{name}.npy")
+        assert x.dtype == np.float32 and x.shape == shape and np.isfinite(x).all(), name
+        if name != "completion_token_ids":   # (a tiny greedy model may repeat a 4-token answer)
+            assert len({r.tobytes() for r in x}) == 4, name   # a row per question, all different
+        assert np.allclose(x, y, rtol=1e-5, atol=1e-5), (name, np.abs(x - y).max())
+    sims = np.load(tmp_path / "a" / "knn_similarity.npy")
+    # best first; a cosine of two normalised vectors each rounded to the store's bf16: <= (1 + 2^-8)^2
+    assert (np.diff(sims, axis=1) <= 0).all() and (sims <= (1 + 2.0 ** -8) ** 2).all()
+    assert (np.load(tmp_path / "a" / "completion_logprobs.npy") < 0).all()
+    toks = np.load(tmp_path / "a" / "completion_token_ids.npy")
+    assert (toks >= 0).all() and (toks == np.round(toks)).all()
+    assert np.array_equal(toks, np.load(tmp_path / "c" / "completion_token_ids.npy"))
+
+
 def test_bench_config2_embeddings_agent_on_kafka_two_ranks(tmp_path):
     """BASELINE config 2 shape: compute-ai-embeddings agent replicas (3 agent-pod processes
     per rank, the bench default) as ONE consumer group on a Kafka topic of the in-tree

@@ -1,7 +1,7 @@
 """Reference fixtures of the text-processing agents, ported:
 TXT tests TextChunkerAgentTest.java:87-127, LanguageDetectorTest.java:37-39 and
-TextExtractorTest.java (the PDF / DOCX fixtures are read from the reference checkout
-when it is present; they are not copied into this repository).
+TextExtractorTest.java (its two small PDF / DOCX documents are stored under
+tests/golden/text_extractor/).
 
 cl100k parity: no cl100k_base rank file exists offline, so the native BPE counter is a
 synthetic-vocabulary byte-level BPE and its counts differ from tiktoken's ("parity
@@ -17,7 +17,7 @@ from langstream_amd.agents.text import LanguageDetectorAgent, RecursiveCharacter
     TextSplitterAgent
 from langstream_amd.api.record import SimpleRecord
 
-RES = "/root/reference/langstream-agents/langstream-agents-text-processing/src/test/resources"
+RES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "text_extractor")
 
 
 def _chunks(cfg, text):
@@ -94,7 +94,6 @@ def test_text_extractor_plain_text_fixture():
     assert out[0].value().strip() == "This is a test"
 
 
-@pytest.mark.skipif(not os.path.isdir(RES), reason="reference checkout not present")
 @pytest.mark.parametrize("fn,expected", [("simple.pdf", "This is a very simple PDF"),
                                          ("simple.docx", "This is a very simple Word Document")])
 def test_text_extractor_binary_fixtures(fn, expected):
