@@ -133,8 +133,10 @@ _PGEMM_MIN_T = int(os.environ.get("LS_PGEMM_MIN_T", "8192"))   # below: hipBLASL
 
 
 def _pgemm(x: torch.Tensor, w: torch.Tensor, silu: bool) -> bool:
-    """Prefill-sized rows on the GPU go to the 256x256-tile MFMA GEMM (same rule as
-    runner.hip's pgemm())."""
+    """The Python forward's own rule (not runner.hip's): bf16 rows on the GPU go to the
+    256x256-tile MFMA GEMM from LS_PGEMM_MIN_T rows (default 8192 here, 1024 in the
+    runner).  LS_PGEMM unset, "1" or any other word: gate_up only; "all": the plain
+    projections too; "0": none."""
     return (_PGEMM > (0 if silu else 1) and x.is_cuda and x.shape[0] >= _PGEMM_MIN_T and x.dtype == torch.bfloat16
             and x.stride(-1) == 1 and ops.hip().gemm_prefill_supported(w, silu))
 

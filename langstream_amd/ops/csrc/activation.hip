@@ -4,7 +4,7 @@
 //  bias_gelu    : x[t, f]   = gelu_erf(x[t, f] + bias[f])      (BERT FFN1 epilogue, in place)
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "ops.h"
 
 namespace {
 

@@ -28,7 +28,7 @@
 #include <torch/csrc/distributed/c10d/ProcessGroup.hpp>
 #include <hip/hip_runtime.h>
 #include <vector>
-#include "common.h"
+#include "ops.h"
 
 namespace py = pybind11;
 

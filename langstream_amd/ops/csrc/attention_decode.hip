@@ -50,7 +50,7 @@
 // (106 us), amdgpu_waves_per_eu(3) (106.9 us).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "ops.h"
 
 namespace {
 
@@ -457,7 +457,7 @@ __global__ void __launch_bounds__(256) decode_merge_kernel(bf16* __restrict__ ou
 
 // Number of KV splits a decode launch over B sequences uses (<= nsplit_max).
 int64_t decode_nsplit(int64_t B, int64_t Hkv, int64_t nsplit_max) {
-  static const int64_t target = getenv("LS_ATTN_TARGET_WG") ? atoll(getenv("LS_ATTN_TARGET_WG")) : TARGET_WG;
+  static const int64_t target = env_int("LS_ATTN_TARGET_WG", TARGET_WG);
   const int64_t pairs = std::max<int64_t>(1, B * Hkv);
   return std::max<int64_t>(1, std::min<int64_t>(nsplit_max, (target + pairs - 1) / pairs));
 }
@@ -502,8 +502,8 @@ static void decode_attention_launch(at::Tensor& out, const at::Tensor& q, const 
   // the chip (256 CUs x 8 resident waves): each wave then streams its whole context
   // with no LDS merge and no idle waves in a workgroup whose block count is not a
   // multiple of 4.  Smaller batches keep 4 waves per pair (and split long contexts).
-  static const int env_wpp = getenv("LS_ATTN_WPP") ? atoi(getenv("LS_ATTN_WPP")) : 0;
-  static const bool pipe = getenv("LS_ATTN_PIPE") ? atoi(getenv("LS_ATTN_PIPE")) != 0 : true;
+  static const int env_wpp = env_int("LS_ATTN_WPP", 0);
+  static const bool pipe = env_flag("LS_ATTN_PIPE", true);
   const bool rope = ra != nullptr;
   // LS_ATTN_NT (read per launch, A/B inside one process): 0 cached loads, 1 all nt, 2
   // (default) nt except each sequence's first block (the shared template-prefix block).
@@ -513,8 +513,7 @@ static void decode_attention_launch(at::Tensor& out, const at::Tensor& q, const 
   // whole RAG bench ran less GPU time with 2 in both rounds of a same-box A/B (16.55 /
   // 16.63 s vs 16.74 / 17.25 s, ab_head_attn_r5ai.log): the decode GEMMs that follow
   // lose more than the attention gains.
-  const char* ent = getenv("LS_ATTN_NT");
-  const int attn_nt = ent ? atoi(ent) : 2;
+  const int attn_nt = env_int("LS_ATTN_NT", 2);
   const RopeArgs rargs = rope ? *ra : RopeArgs{};
   const int wpp = env_wpp == 1 || env_wpp == 4 ? env_wpp : ((int64_t)B * Hkv >= WAVE_SLOTS && ns == 1 ? 1 : 4);
   dim3 grid(B * Hkv, ns);

@@ -18,7 +18,7 @@
 // both fragment reads are bank-conflict-free (derivation in the comments below).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "ops.h"
 
 namespace {
 

@@ -1,102 +1,5 @@
 // Python bindings for the langstream_amd HIP kernels (module `_hip_ops`).
-#include <torch/extension.h>
-
-void rmsnorm(at::Tensor out, at::Tensor x, at::Tensor w, double eps);
-void fused_add_rmsnorm(at::Tensor x, at::Tensor residual, at::Tensor w, double eps);
-void layernorm(at::Tensor out, at::Tensor x, c10::optional<at::Tensor> bias, c10::optional<at::Tensor> residual,
-               at::Tensor g, at::Tensor b, double eps);
-void embed_layernorm(at::Tensor out, at::Tensor ids, at::Tensor pos_ids, c10::optional<at::Tensor> type_ids,
-                     at::Tensor wte, at::Tensor wpe, at::Tensor wtt, at::Tensor g, at::Tensor b, double eps);
-void silu_and_mul(at::Tensor out, at::Tensor x);
-void bias_gelu(at::Tensor x, c10::optional<at::Tensor> bias);
-void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache,
-                    at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope);
-void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
-                            at::Tensor block_tables, at::Tensor ctx_lens, double scale, int64_t nsplit,
-                            int64_t blocks_per_split, at::Tensor workspace);
-void paged_decode_attention_rope(at::Tensor out, at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin,
-                                 at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, at::Tensor block_tables,
-                                 at::Tensor ctx_lens, double scale, int64_t nsplit, int64_t min_bps,
-                                 at::Tensor workspace);
-void paged_prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
-                             at::Tensor block_tables, at::Tensor q_start, at::Tensor q_len, at::Tensor ctx_len,
-                             at::Tensor tiles, int64_t Hq, double scale);
-void varlen_encoder_attention(at::Tensor out, at::Tensor qkv, at::Tensor q_start, at::Tensor q_len,
-                              at::Tensor tiles, int64_t Hq, int64_t Hkv, double scale);
-void sample_tokens(at::Tensor logits, at::Tensor temperature, at::Tensor top_k, at::Tensor top_p, at::Tensor seeds,
-                   at::Tensor steps, at::Tensor out_tok, at::Tensor out_lp, at::Tensor top_ids, at::Tensor top_lps,
-                   int64_t n_top);
-void apply_logit_deltas(at::Tensor logits, at::Tensor rows, at::Tensor toks, at::Tensor delta);
-void pool_embeddings(at::Tensor out, at::Tensor x, at::Tensor start, at::Tensor len, int64_t mode, bool normalize);
-void l2_normalize_rows(at::Tensor out, at::Tensor x);
-void tp_sample_stats(at::Tensor logits, int64_t vstart, at::Tensor stats);
-void tp_sample_hist(at::Tensor logits, int64_t vtot, at::Tensor temperature, at::Tensor top_k, at::Tensor top_p,
-                    at::Tensor stats_all, int64_t world, at::Tensor hist);
-void tp_sample_pick(at::Tensor logits, int64_t vstart, int64_t vtot, at::Tensor temperature, at::Tensor top_k,
-                    at::Tensor top_p, at::Tensor seeds, at::Tensor steps, at::Tensor stats_all, int64_t world,
-                    at::Tensor hist_all, int64_t n_top, at::Tensor cand);
-void tp_sample_final(at::Tensor stats_all, at::Tensor cand_all, int64_t world, int64_t rows, at::Tensor temperature,
-                     int64_t n_top, at::Tensor out_tok, at::Tensor out_lp, at::Tensor top_ids, at::Tensor top_lps);
-std::vector<at::Tensor> oneshot_allreduce_sim(std::vector<at::Tensor> inputs, int64_t calls, int64_t stall_rank);
-int64_t oneshot_allreduce_selftest(py::object process_group, at::Tensor t);
-bool oneshot_flags_uncached(py::object process_group);
-std::vector<at::Tensor> oneshot_collectives_selftest(py::object process_group, at::Tensor bf, at::Tensor g32,
-                                                     at::Tensor i64, int64_t cap);
-std::vector<at::Tensor> oneshot_route_selftest(py::object process_group, at::Tensor g32, at::Tensor i64, int64_t cap);
-void knn_topk(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::Tensor out_i, at::Tensor ws_s,
-              at::Tensor ws_i, int64_t sample);
-void knn_topk_ablate(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::Tensor out_i, at::Tensor ws_s,
-                     at::Tensor ws_i, int64_t sample, int64_t abl);
-int64_t knn_default_sample();
-void skinny_gemm(at::Tensor out, at::Tensor x, at::Tensor w);
-void gemv(at::Tensor out, at::Tensor x, at::Tensor w);
-bool gemv_supported(const at::Tensor& w, bool silu);
-void gemv_silu(at::Tensor out, at::Tensor x, at::Tensor w);
-void gemv_add_rmsnorm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor residual, at::Tensor norm_w,
-                      double eps, at::Tensor counter);
-void gemv_norm(at::Tensor out, at::Tensor o, at::Tensor res, at::Tensor res_out, at::Tensor norm_w, double eps,
-               at::Tensor w);
-void gemv_silu_norm(at::Tensor out, at::Tensor o, at::Tensor res, at::Tensor res_out, at::Tensor norm_w, double eps,
-                    at::Tensor w);
-void gemv_qkv(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots,
-              at::Tensor k_cache, at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope,
-              c10::optional<at::Tensor> o, c10::optional<at::Tensor> res, c10::optional<at::Tensor> res_out,
-              c10::optional<at::Tensor> norm_w, double eps);
-void skinny_gemm_silu(at::Tensor out, at::Tensor x, at::Tensor w);
-void gemm_fused(at::Tensor out, at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias, bool gelu,
-                c10::optional<at::Tensor> residual, c10::optional<at::Tensor> ln_stats_in, int64_t ln_width,
-                c10::optional<at::Tensor> c1, c10::optional<at::Tensor> c2, c10::optional<at::Tensor> res_g,
-                c10::optional<at::Tensor> res_b, double eps, c10::optional<at::Tensor> stats_out);
-void skinny_gemm_add_rmsnorm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor residual, at::Tensor norm_w,
-                             double eps);
-void gemm_prefill(at::Tensor out, at::Tensor x, at::Tensor w, bool silu, int64_t variant);
-bool gemm_prefill_supported(const at::Tensor& w, bool silu);
-void gemm_prefill_f32(at::Tensor out, at::Tensor x, at::Tensor w);
-bool gemm_prefill_f32_supported(const at::Tensor& w);
-bool decode_gemm_supported(const at::Tensor& w, bool silu);
-int64_t decode_gemm_workspace(int64_t M, int64_t N, int64_t K, bool silu);
-void decode_gemm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspace, c10::optional<at::Tensor> residual,
-                 c10::optional<at::Tensor> norm_w, double eps, int64_t bn_force, int64_t splits_force);
-void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor pos,
-                          at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, int64_t Hq,
-                          int64_t Hkv);
-bool decode_gemm_f32_supported(const at::Tensor& w, int64_t M);
-void decode_gemm_f32(at::Tensor out, at::Tensor x, at::Tensor w, int64_t bn_force);
-void decode_gemm_silu(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor tickets,
-                      at::Tensor err, int64_t splits);
-void decode_gemm_ablate(at::Tensor x, at::Tensor w, at::Tensor workspace, int64_t abl, int64_t splits,
-                        int64_t split_outer);
-int64_t decode_gemm_cmb_splits(int64_t N, int64_t K);
-void decode_gemm_res(at::Tensor y_out, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor counters,
-                     at::Tensor residual, at::Tensor norm_g, at::Tensor sumsq_out, at::Tensor err);
-void decode_gemm_qkv_cmb(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor counters,
-                         at::Tensor sumsq_in, double eps, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots,
-                         at::Tensor k_cache, at::Tensor v_cache, int64_t Hq, int64_t Hkv, at::Tensor err);
-void decode_gemm_silu_r(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor sumsq_in, double eps);
-pybind11::dict decode_gemm_launch_counts(bool reset);
-void rms_prep(at::Tensor y, at::Tensor sumsq, at::Tensor h, at::Tensor g);
-void rows_rms_scale(at::Tensor out, at::Tensor y, at::Tensor sumsq, double eps);
-void bind_runners(pybind11::module_& m);
+#include "ops.h"
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "langstream_amd CDNA4 (gfx950) kernels";

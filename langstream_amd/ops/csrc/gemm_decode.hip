@@ -37,11 +37,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <atomic>
 #include <string>
-#include "common.h"
-
-void splitk_reduce_launch(const float* part, int S, int M, int N, bf16* out, int64_t ldo, hipStream_t st);
-void splitk_add_rmsnorm_launch(const float* part, int S, int M, int N, bf16* residual, const bf16* norm_w, float eps,
-                               bf16* out, hipStream_t st);
+#include "ops.h"
 
 namespace {
 
@@ -599,11 +595,6 @@ __global__ void __launch_bounds__(LD ? 768 : 512) dgemm_kernel(const bf16* __res
   }
 }
 
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 // Splits so that tiles x S covers the chip about once (<= 256 + 8 workgroups, one per
 // CU) with at least `min_steps` 64-deep stages per split.
 int pick_split(int tiles, int K, int min_steps) {
@@ -890,9 +881,6 @@ __global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(
     }
   }
 }
-
-void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache,
-                    at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope);
 
 // qkv[M, (Hq + 2 Hkv) D] = RoPE(x . w^T) for q and k heads, with the step's K / V rows
 // written to the paged cache (the same contract as decode_gemm + rope_and_cache).

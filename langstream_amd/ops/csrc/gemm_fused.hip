@@ -24,7 +24,7 @@
 // RES: v += res [normalised when RESLN]; store bf16; STATS: per-row partial sums.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "ops.h"
 
 namespace {
 
@@ -200,10 +200,7 @@ __global__ void __launch_bounds__(BM * 2) gemm_fused_kernel(const bf16* __restri
 // K (encoder: 12-48 stages) runs a 3-deep ring at 2 workgroups per CU, overlapping one
 // workgroup's prologue / epilogue with another's main loop; LS_GEMM_RING overrides.
 int ring_depth(int bm, int nk) {
-  static const int env = [] {
-    const char* v = getenv("LS_GEMM_RING");
-    return v ? atoi(v) : 0;
-  }();
+  static const int env = env_int("LS_GEMM_RING", 0);
   if (env == 3 || env == 4 || env == 6) return env;
   if (bm == 256) return nk <= 48 ? 3 : 6;
   return nk <= 48 ? 3 : 4;

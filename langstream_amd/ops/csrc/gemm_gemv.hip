@@ -21,7 +21,7 @@
 // writes silu(gate) * up as [T, F] (replacing the gate_up GEMM + silu_and_mul pair).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "ops.h"
 
 namespace {
 

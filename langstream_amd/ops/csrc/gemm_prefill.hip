@@ -22,7 +22,7 @@
 //     accumulators; out = silu(g) * u is stored as bf16 [M, F].
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "ops.h"
 #include <type_traits>
 
 namespace {
@@ -819,11 +819,6 @@ int num_cus() {
   return n;
 }
 
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 template <int EPI>
 void launch(int variant, int ring, int nwv, bool sp, dim3 grid, hipStream_t st, const at::Tensor& x, const at::Tensor& w, int M, int K,
             at::Tensor& out, int MT, int NTL, int F, int gm) {
@@ -853,7 +848,7 @@ void launch(int variant, int ring, int nwv, bool sp, dim3 grid, hipStream_t st, 
       gemm_pp_kernel<EPI, 0><<<grid, 512, 0, st>>>(xp, x.stride(0), wp, M, K, op, out.stride(0), MT, NTL, F, gm);
     return;
   }
-  static const bool k64 = env_int("LS_PGEMM_K64", 0) != 0;   // measured equal, 2-slot ring: off
+  static const bool k64 = env_flag("LS_PGEMM_K64", false);   // measured equal, 2-slot ring: off
   if (k64 && K % 64 == 0) {
     gemm_prefill64_kernel<EPI><<<grid, 512, 0, st>>>((const bf16*)x.data_ptr(), x.stride(0),
                                                     (const bf16*)w.data_ptr(), M, K, (bf16*)out.data_ptr(),
@@ -892,8 +887,6 @@ void launch(int variant, int ring, int nwv, bool sp, dim3 grid, hipStream_t st, 
 
 // Shapes the kernel takes: K % 32 == 0 and N % 256 == 0 (silu: the fused [2F, K] gate_up
 // weight with F % 128 == 0).
-void splitk_reduce_launch(const float* part, int S, int M, int N, bf16* out, int64_t ldo, hipStream_t st);
-
 bool gemm_prefill_supported(const at::Tensor& w, bool silu) {
   if (w.dim() != 2 || w.scalar_type() != at::kBFloat16 || !w.is_contiguous() || w.size(1) % GBK != 0) return false;
   return silu ? (w.size(0) % 256 == 0) : (w.size(0) % TN == 0);
@@ -920,7 +913,7 @@ void gemm_prefill(at::Tensor out, at::Tensor x, at::Tensor w, bool silu, int64_t
   static const int ring = env_int("LS_PGEMM_RING", 4);
   static const int gm_env = env_int("LS_PGEMM_GROUP", 8);
   static const int nwv = env_int("LS_PGEMM_WAVES", 8) == 4 ? 4 : 8;
-  static const bool sp = env_int("LS_PGEMM_SPREAD", 1) != 0;
+  static const bool sp = env_flag("LS_PGEMM_SPREAD", true);
   const int gm = std::max(1, std::min(gm_env, MT));
   auto stream = at::hip::getCurrentHIPStream();
   const dim3 grid((unsigned)(MT * NTL));

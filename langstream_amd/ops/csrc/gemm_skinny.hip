@@ -22,7 +22,7 @@
 //     RMSNorm in the split-K reduction for o_proj / down_proj.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "ops.h"
 
 namespace {
 
@@ -377,10 +377,7 @@ __global__ void __launch_bounds__(BM * 2) skinny_glds_kernel(const bf16* __restr
 }
 
 bool use_glds() {
-  static const bool on = [] {
-    const char* e = getenv("LS_SKINNY_GLDS");
-    return e == nullptr || e[0] != '0';
-  }();
+  static const bool on = env_flag("LS_SKINNY_GLDS", true);
   return on;
 }
 
@@ -501,8 +498,8 @@ void splitk_add_rmsnorm_launch(const float* part, int S, int M, int N, bf16* res
                                bf16* out, hipStream_t st) {
   const int nv = (N / 8 + 255) / 256;
   TORCH_CHECK(nv <= 8, "splitk_add_rmsnorm: N <= 16384");
-  const char* e = getenv("LS_NORM_NT512");   // 0: the 256-thread form (read per launch, A/B in one process)
-  if ((e ? atoi(e) : 1) != 0 && N / 8 <= 512) {
+  // LS_NORM_NT512=0: the 256-thread form (read per launch, A/B in one process)
+  if (env_flag("LS_NORM_NT512", true) && N / 8 <= 512) {
     splitk_add_rmsnorm_kernel<1, 8, 512><<<M, 512, 0, st>>>(part, S, M, N, residual, norm_w, eps, out);
     return;
   }

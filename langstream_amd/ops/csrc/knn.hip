@@ -21,7 +21,7 @@
 // cosine similarity.  Rows >= N (tail chunk) score -inf.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "ops.h"
 
 namespace {
 
@@ -664,7 +664,7 @@ template <int DD, int MM>
 void launch_q256(int abl, dim3 grid, hipStream_t stream, const bf16* X, int64_t N, const bf16* Q, int Qn, float* ws_s,
                  int32_t* ws_i, int* ctrl, int64_t cap, int64_t row_begin, int rpw, int nqb, int G) {
   // LS_KNN_PRIO: 2 (default) MFMA clusters at raised priority, 1 half the waves raised, 0 none
-  static const int prio = getenv("LS_KNN_PRIO") ? atoi(getenv("LS_KNN_PRIO")) : 2;
+  static const int prio = env_int("LS_KNN_PRIO", 2);
   // the timing-only ablations exist for the bench's shape (384 dims, main pass) only
   if constexpr (DD == 384 && MM == 1) {
     switch (abl) {
@@ -871,7 +871,7 @@ void knn_topk_impl(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::
     DISPATCH_DIM(LAUNCH_E)
 #undef LAUNCH_E
   };
-  static const int q256_min = getenv("LS_KNN_Q256_MIN") ? atoi(getenv("LS_KNN_Q256_MIN")) : 128;
+  static const int q256_min = env_int("LS_KNN_Q256_MIN", 128);
   const bool q256 = Qn >= q256_min && (dim == 128 || dim == 256 || dim == 384 || dim == 512);
   // MODE: 0 strict filter after an exact sample, 1 non-strict filter over the whole store,
   // 2 group-max sample pass (gmax = ws_s scratch, G groups per query)
@@ -935,6 +935,8 @@ void knn_topk_impl(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::
   // MFMA pass with a running-max epilogue, ~10x cheaper than the exact per-chunk top-K
   // of the sample) and the filter then covers the whole store with scores >= thr.
   const int64_t S = (int64_t)ns * CH;
+  // LS_KNN_EXACT_SAMPLE is a presence test (set to anything, "0" included: the exact
+  // sample), read per call -- hence the raw getenv
   if (q256 && ns < nchunks && K <= 64 && N >= 2 * S && !getenv("LS_KNN_EXACT_SAMPLE")) {
     const int nqb = (Qn + 255) / 256;
     const int64_t nrb_target = std::min<int64_t>(256, std::max<int64_t>(32, 256 / nqb));

@@ -7,7 +7,7 @@
 //  embed_layernorm    : y = LN(word[id] + pos[p] + type[t]) * g + b        (BERT input)
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "ops.h"
 
 namespace {
 

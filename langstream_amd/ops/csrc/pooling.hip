@@ -6,7 +6,7 @@
 // One workgroup (256 threads) per sequence, 16-B vector loads over H.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "ops.h"
 
 namespace {
 

@@ -18,7 +18,7 @@
 // (T/16) x (Hq/8 + Hkv/8 + Hkv) workgroups instead of one.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "ops.h"
 
 namespace {
 

@@ -23,12 +23,10 @@
 //   graph of gather+forward+deltas+sample; the counts those kernels need are read
 //   from the device copy of the arena header, so one graph serves every step of its
 //   bucket.  Non-zero TP ranks run worker_loop() entirely in C++.
-#include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <ATen/hip/HIPGraph.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
-#include <torch/csrc/distributed/c10d/ProcessGroup.hpp>
 
 #include <chrono>
 #include <condition_variable>
@@ -40,6 +38,8 @@
 #include <memory>
 #include <string>
 #include <vector>
+
+#include "ops.h"
 
 namespace py = pybind11;
 
@@ -64,98 +64,6 @@ bool use_pp(int64_t T, int64_t N, int64_t K) {
   return b >= 0 && b < (int64_t)it->second.size() && it->second[b] != 0;
 }
 }  // namespace pgemm_route
-
-void rmsnorm(at::Tensor out, at::Tensor x, at::Tensor w, double eps);
-void fused_add_rmsnorm(at::Tensor x, at::Tensor residual, at::Tensor w, double eps);
-void layernorm(at::Tensor out, at::Tensor x, c10::optional<at::Tensor> bias, c10::optional<at::Tensor> residual,
-               at::Tensor g, at::Tensor b, double eps);
-void embed_layernorm(at::Tensor out, at::Tensor ids, at::Tensor pos_ids, c10::optional<at::Tensor> type_ids,
-                     at::Tensor wte, at::Tensor wpe, at::Tensor wtt, at::Tensor g, at::Tensor b, double eps);
-void silu_and_mul(at::Tensor out, at::Tensor x);
-void bias_gelu(at::Tensor x, c10::optional<at::Tensor> bias);
-void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache,
-                    at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope);
-void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
-                            at::Tensor block_tables, at::Tensor ctx_lens, double scale, int64_t nsplit,
-                            int64_t blocks_per_split, at::Tensor workspace);
-void paged_decode_attention_rope(at::Tensor out, at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin,
-                                 at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, at::Tensor block_tables,
-                                 at::Tensor ctx_lens, double scale, int64_t nsplit, int64_t min_bps,
-                                 at::Tensor workspace);
-void paged_prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
-                             at::Tensor block_tables, at::Tensor q_start, at::Tensor q_len, at::Tensor ctx_len,
-                             at::Tensor tiles, int64_t Hq, double scale);
-void varlen_encoder_attention(at::Tensor out, at::Tensor qkv, at::Tensor q_start, at::Tensor q_len,
-                              at::Tensor tiles, int64_t Hq, int64_t Hkv, double scale);
-void pool_embeddings(at::Tensor out, at::Tensor x, at::Tensor start, at::Tensor len, int64_t mode, bool normalize);
-void sample_tokens(at::Tensor logits, at::Tensor temperature, at::Tensor top_k, at::Tensor top_p, at::Tensor seeds,
-                   at::Tensor steps, at::Tensor out_tok, at::Tensor out_lp, at::Tensor top_ids, at::Tensor top_lps,
-                   int64_t n_top);
-void tp_sample_stats(at::Tensor logits, int64_t vstart, at::Tensor stats);
-void tp_sample_hist(at::Tensor logits, int64_t vtot, at::Tensor temperature, at::Tensor top_k, at::Tensor top_p,
-                    at::Tensor stats_all, int64_t world, at::Tensor hist);
-void tp_sample_pick(at::Tensor logits, int64_t vstart, int64_t vtot, at::Tensor temperature, at::Tensor top_k,
-                    at::Tensor top_p, at::Tensor seeds, at::Tensor steps, at::Tensor stats_all, int64_t world,
-                    at::Tensor hist_all, int64_t n_top, at::Tensor cand);
-void tp_sample_final(at::Tensor stats_all, at::Tensor cand_all, int64_t world, int64_t rows, at::Tensor temperature,
-                     int64_t n_top, at::Tensor out_tok, at::Tensor out_lp, at::Tensor top_ids, at::Tensor top_lps);
-
-class OneShotAllReduce;
-std::shared_ptr<OneShotAllReduce> make_oneshot_allreduce(c10::intrusive_ptr<::c10d::ProcessGroup> pg,
-                                                         int64_t max_elems);
-void oneshot_allreduce_run(const std::shared_ptr<OneShotAllReduce>& ar, at::Tensor t);
-void oneshot_allreduce_i64(const std::shared_ptr<OneShotAllReduce>& ar, at::Tensor t);
-void oneshot_allgather32(const std::shared_ptr<OneShotAllReduce>& ar, const at::Tensor& in, at::Tensor out);
-int64_t oneshot_capacity_bytes(const std::shared_ptr<OneShotAllReduce>& ar);
-bool oneshot_route_sum_i64(const std::shared_ptr<OneShotAllReduce>& ar,
-                           const c10::intrusive_ptr<::c10d::ProcessGroup>& pg, at::Tensor t);
-bool oneshot_route_gather32(const std::shared_ptr<OneShotAllReduce>& ar,
-                            const c10::intrusive_ptr<::c10d::ProcessGroup>& pg, const at::Tensor& src,
-                            const at::Tensor& dst);
-
-void skinny_gemm(at::Tensor out, at::Tensor x, at::Tensor w);
-void gemm_fused(at::Tensor out, at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias, bool gelu,
-                c10::optional<at::Tensor> residual, c10::optional<at::Tensor> ln_stats_in, int64_t ln_width,
-                c10::optional<at::Tensor> c1, c10::optional<at::Tensor> c2, c10::optional<at::Tensor> res_g,
-                c10::optional<at::Tensor> res_b, double eps, c10::optional<at::Tensor> stats_out);
-void gemv(at::Tensor out, at::Tensor x, at::Tensor w);
-void gemv_silu(at::Tensor out, at::Tensor x, at::Tensor w);
-bool gemv_supported(const at::Tensor& w, bool silu);
-void gemv_norm(at::Tensor out, at::Tensor o, at::Tensor res, at::Tensor res_out, at::Tensor norm_w, double eps,
-               at::Tensor w);
-void gemv_qkv(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots,
-              at::Tensor k_cache, at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope,
-              c10::optional<at::Tensor> o, c10::optional<at::Tensor> res, c10::optional<at::Tensor> res_out,
-              c10::optional<at::Tensor> norm_w, double eps);
-void gemv_silu_norm(at::Tensor out, at::Tensor o, at::Tensor res, at::Tensor res_out, at::Tensor norm_w, double eps,
-                    at::Tensor w);
-void skinny_gemm_add_rmsnorm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor residual, at::Tensor norm_w,
-                             double eps);
-void gemm_prefill(at::Tensor out, at::Tensor x, at::Tensor w, bool silu, int64_t variant);
-bool gemm_prefill_supported(const at::Tensor& w, bool silu);
-void gemm_prefill_f32(at::Tensor out, at::Tensor x, at::Tensor w);
-bool gemm_prefill_f32_supported(const at::Tensor& w);
-bool decode_gemm_supported(const at::Tensor& w, bool silu);
-int64_t decode_gemm_workspace(int64_t M, int64_t N, int64_t K, bool silu);
-void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor pos,
-                          at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, int64_t Hq,
-                          int64_t Hkv);
-bool decode_gemm_f32_supported(const at::Tensor& w, int64_t M);
-void decode_gemm_f32(at::Tensor out, at::Tensor x, at::Tensor w, int64_t bn_force);
-void decode_gemm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspace, c10::optional<at::Tensor> residual,
-                 c10::optional<at::Tensor> norm_w, double eps, int64_t bn_force, int64_t splits_force);
-void decode_gemm_silu(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor tickets,
-                      at::Tensor err, int64_t splits);
-const int* oneshot_allreduce_err(const std::shared_ptr<OneShotAllReduce>& ar);
-int64_t decode_gemm_cmb_splits(int64_t N, int64_t K);
-void decode_gemm_res(at::Tensor y_out, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor counters,
-                     at::Tensor residual, at::Tensor norm_g, at::Tensor sumsq_out, at::Tensor err);
-void decode_gemm_qkv_cmb(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor counters,
-                         at::Tensor sumsq_in, double eps, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots,
-                         at::Tensor k_cache, at::Tensor v_cache, int64_t Hq, int64_t Hkv, at::Tensor err);
-void decode_gemm_silu_r(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor sumsq_in, double eps);
-void rms_prep(at::Tensor y, at::Tensor sumsq, at::Tensor h, at::Tensor g);
-void rows_rms_scale(at::Tensor out, at::Tensor y, at::Tensor sumsq, double eps);
 
 #define HIP_OK(x)                                                                  \
   do {                                                                             \
@@ -198,9 +106,10 @@ class LlamaRunner {
                 "inconsistent layer lists");
     if (!process_group.is_none()) pg_ = py::cast<c10::intrusive_ptr<::c10d::ProcessGroup>>(process_group);
     // LS_ONESHOT_AR=1: decode-sized all-reduces (<= LS_ONESHOT_AR_MAX elements, default
-    // 256 x 8192) through the one-shot IPC kernel (allreduce.hip) instead of RCCL
-    if (pg_ && getenv("LS_ONESHOT_AR") && atoi(getenv("LS_ONESHOT_AR")) != 0) {
-      const int64_t mx = getenv("LS_ONESHOT_AR_MAX") ? atoll(getenv("LS_ONESHOT_AR_MAX")) : 256 * 8192;
+    // 256 x 8192) through the one-shot IPC kernel (allreduce.hip) instead of RCCL.  Both
+    // are read per construction (tests set them after import).
+    if (pg_ && env_flag("LS_ONESHOT_AR", false)) {
+      const int64_t mx = env_int("LS_ONESHOT_AR_MAX", 256 * 8192);
       oneshot_ = make_oneshot_allreduce(pg_, mx);
       oneshot_max_ = mx;
     }
@@ -292,10 +201,7 @@ class LlamaRunner {
   // 256 rows; only shapes it cannot take (vocab % 128, hidden % 64) fall back to the
   // library GEMM (LS_DGEMM_HEAD=0 forces the library).
   at::Tensor lm_head(const at::Tensor& x) {
-    static const bool dg_head = [] {
-      const char* e = getenv("LS_DGEMM_HEAD");
-      return e == nullptr || e[0] != '0';
-    }();
+    static const bool dg_head = env_flag("LS_DGEMM_HEAD", true);
     const int64_t R = x.size(0);
     // LS_HEAD_PP_MIN_T = n > 0: batches of n+ rows on the ping-pong prefill kernel with an
     // f32 epilogue -- faster alone (261 vs 279 us at M = 256, 247 vs 268 at 192:
@@ -303,10 +209,7 @@ class LlamaRunner {
     // was 1.8 % lower with it in all three rounds of a same-box A/B (ab_head_r5ak.log; it
     // streams the 1 GB head through the caches, where the decode GEMM's loads are
     // non-temporal).  Off by default.
-    static const int64_t pp_min = [] {
-      const char* e = getenv("LS_HEAD_PP_MIN_T");
-      return e ? atoll(e) : 0;
-    }();
+    static const int64_t pp_min = env_int("LS_HEAD_PP_MIN_T", 0);
     if (pp_min > 0 && R >= pp_min && gemm_prefill_f32_supported(lm_head_) &&
         (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0 && x.stride(1) == 1 && x.stride(0) % 8 == 0) {
       at::Tensor out = at::empty({R, lm_head_.size(0)}, x.options().dtype(at::kFloat));
@@ -316,10 +219,9 @@ class LlamaRunner {
     if (dg_head && dgemm_enabled() && R >= 1 && decode_gemm_f32_supported(lm_head_, std::min<int64_t>(R, kDgemmMaxM))) {
       at::Tensor xc = x.contiguous();
       at::Tensor out = at::empty({R, lm_head_.size(0)}, x.options().dtype(at::kFloat));
-      for (int64_t r0 = 0; r0 < R; r0 += kDgemmMaxM) {
-        const int64_t n = std::min<int64_t>(kDgemmMaxM, R - r0);
+      dgemm_blocks(R, [&](int64_t r0, int64_t n) {
         decode_gemm_f32(out.narrow(0, r0, n), xc.narrow(0, r0, n), lm_head_, 0);
-      }
+      });
       return out;
     }
     if (f32_head_) {
@@ -344,10 +246,9 @@ class LlamaRunner {
     } else if (plib(T, w)) {
       at::linear_out(out, x, w);
     } else if (dgemm_blocks_ok(w, false) && x.stride(1) == 1) {
-      for (int64_t r0 = 0; r0 < T; r0 += kDgemmMaxM) {
-        const int64_t n = std::min<int64_t>(kDgemmMaxM, T - r0);
+      dgemm_blocks(T, [&](int64_t r0, int64_t n) {
         decode_gemm(out.narrow(0, r0, n), x.narrow(0, r0, n), w, dg_ws_, c10::nullopt, c10::nullopt, eps_, 0, 0);
-      }
+      });
     } else {
       out = at::linear(x, w);
     }
@@ -361,10 +262,9 @@ class LlamaRunner {
     if (pgemm(T, w, true)) {
       gemm_prefill(a, x, w, true, -1);
     } else if (dgemm_blocks_ok(w, true) && x.stride(1) == 1) {
-      for (int64_t r0 = 0; r0 < T; r0 += kDgemmMaxM) {
-        const int64_t n = std::min<int64_t>(kDgemmMaxM, T - r0);
+      dgemm_blocks(T, [&](int64_t r0, int64_t n) {
         decode_gemm_silu(a.narrow(0, r0, n), x.narrow(0, r0, n), w, dg_ws_, dg_tickets_, status_.narrow(0, 0, 1), 0);
-      }
+      });
     } else {
       at::Tensor gu = at::linear(x, w);
       silu_and_mul(a, gu);
@@ -398,10 +298,18 @@ class LlamaRunner {
     // (ops/csrc/gemm_gemv.hip) for all four projections, gate_up with silu*up fused; it
     // fuses no residual, so it also serves tensor-parallel ranks.
     const bool gv = gemv_enabled() && T <= 4;
+    const bool decode_only = num_prefill == 0 && num_decode == T;
+    // roped: RoPE + the K/V cache write already done by the qkv GEMM / GEMV
     auto attend = [&](int64_t l, const at::Tensor& qkv, bool roped) {
+      at::Tensor attn = at::empty({T, hq_ * d_}, qkv.options());
+      if (!roped && decode_only && rope_fused()) {
+        // decode-only step: RoPE + K/V cache write inside the attention kernel
+        paged_decode_attention_rope(attn, qkv, pos, cos_sin_, slots, kc_[l], vc_[l], d_bt, d_ctx, scale_, nsplit,
+                                    bps, ws);
+        return attn;
+      }
       if (!roped) rope_and_cache(qkv, pos, cos_sin_, slots, kc_[l], vc_[l], hq_, hkv_, true);
       at::Tensor q = qkv.narrow(1, 0, hq_ * d_);
-      at::Tensor attn = at::empty({T, hq_ * d_}, qkv.options());
       if (num_decode > 0)
         paged_decode_attention(attn.narrow(0, 0, num_decode), q.narrow(0, 0, num_decode), kc_[l], vc_[l], d_bt,
                                d_ctx, scale_, nsplit, bps, ws);
@@ -455,7 +363,6 @@ class LlamaRunner {
       fused_add_rmsnorm(dn, residual, final_norm_, eps_);
       x = dn;
     }
-    const bool decode_only = num_prefill == 0 && num_decode == T;
     for (int64_t l = 0; l < L && !fused; ++l) {
       at::Tensor qkv;
       bool roped = false;   // RoPE + the K/V cache write already done by the qkv GEMM's reduction
@@ -476,51 +383,8 @@ class LlamaRunner {
       } else {
         qkv = proj(x, qkv_w_[l]);
       }
-      at::Tensor attn = at::empty({T, hq_ * d_}, qkv.options());
-      at::Tensor q = qkv.narrow(1, 0, hq_ * d_);
-      if (roped) {
-        paged_decode_attention(attn, q, kc_[l], vc_[l], d_bt, d_ctx, scale_, nsplit, bps, ws);
-      } else if (decode_only && rope_fused()) {
-        // decode-only step: RoPE + K/V cache write inside the attention kernel
-        paged_decode_attention_rope(attn, qkv, pos, cos_sin_, slots, kc_[l], vc_[l], d_bt, d_ctx, scale_, nsplit,
-                                    bps, ws);
-      } else {
-        rope_and_cache(qkv, pos, cos_sin_, slots, kc_[l], vc_[l], hq_, hkv_, true);
-        if (num_decode > 0)
-          paged_decode_attention(attn.narrow(0, 0, num_decode), q.narrow(0, 0, num_decode), kc_[l], vc_[l], d_bt,
-                                 d_ctx, scale_, nsplit, bps, ws);
-      }
-      if (num_prefill > 0)
-        paged_prefill_attention(attn, q, kc_[l], vc_[l], p_bt, q_start, q_len, ctx_len, tiles, hq_, scale_);
-      at::Tensor o;
-      if (gv && gemv_supported(o_w_[l], false)) {
-        o = at::empty_like(residual);
-        gemv(o, attn, o_w_[l]);
-        all_reduce(o);
-        fused_add_rmsnorm(o, residual, post_norm_[l], eps_);
-      } else if (dgemm(T, o_w_[l], false)) {
-        o = at::empty_like(residual);
-        if (!pg_) {
-          decode_gemm(o, attn, o_w_[l], dg_ws_, residual, post_norm_[l], eps_, 0, 0);
-        } else {
-          decode_gemm(o, attn, o_w_[l], dg_ws_, c10::nullopt, c10::nullopt, eps_, 0, 0);
-          all_reduce(o);
-          fused_add_rmsnorm(o, residual, post_norm_[l], eps_);
-        }
-      } else if (sk && T <= 192 && skinny_shape(o_w_[l])) {
-        o = at::empty_like(residual);
-        if (!pg_) {
-          skinny_gemm_add_rmsnorm(o, attn, o_w_[l], residual, post_norm_[l], eps_);
-        } else {
-          skinny_gemm(o, attn, o_w_[l]);
-          all_reduce(o);
-          fused_add_rmsnorm(o, residual, post_norm_[l], eps_);
-        }
-      } else {
-        o = proj(attn, o_w_[l]);
-        all_reduce(o);
-        fused_add_rmsnorm(o, residual, post_norm_[l], eps_);
-      }
+      at::Tensor attn = attend(l, qkv, roped);
+      at::Tensor o = row_proj(attn, o_w_[l], residual, post_norm_[l], gv, 0, 192);
       at::Tensor a;
       if (gv && gemv_supported(gate_up_w_[l], true)) {
         a = at::empty({T, gate_up_w_[l].size(0) / 2}, o.options());
@@ -533,55 +397,22 @@ class LlamaRunner {
         a = proj_silu(o, gate_up_w_[l]);
       }
       const at::Tensor& nxt = l + 1 < L ? in_norm_[l + 1] : final_norm_;
-      at::Tensor dn;
-      if (gv && gemv_supported(down_w_[l], false)) {
-        dn = at::empty_like(residual);
-        gemv(dn, a, down_w_[l]);
-        all_reduce(dn);
-        fused_add_rmsnorm(dn, residual, nxt, eps_);
-      } else if (dgemm(T, down_w_[l], false)) {
-        dn = at::empty_like(residual);
-        if (!pg_) {
-          decode_gemm(dn, a, down_w_[l], dg_ws_, residual, nxt, eps_, 0, 0);
-        } else {
-          decode_gemm(dn, a, down_w_[l], dg_ws_, c10::nullopt, c10::nullopt, eps_, 0, 0);
-          all_reduce(dn);
-          fused_add_rmsnorm(dn, residual, nxt, eps_);
-        }
-      } else if (sk && T >= 48 && T <= 256 && skinny_shape(down_w_[l])) {
-        dn = at::empty_like(residual);
-        if (!pg_) {
-          skinny_gemm_add_rmsnorm(dn, a, down_w_[l], residual, nxt, eps_);
-        } else {
-          skinny_gemm(dn, a, down_w_[l]);
-          all_reduce(dn);
-          fused_add_rmsnorm(dn, residual, nxt, eps_);
-        }
-      } else {
-        dn = proj(a, down_w_[l]);
-        all_reduce(dn);
-        fused_add_rmsnorm(dn, residual, nxt, eps_);
-      }
-      x = dn;
+      x = row_proj(a, down_w_[l], residual, nxt, gv, 48, 256);
     }
-    at::Tensor sel = rows.has_value() ? x.index_select(0, *rows) : x;
-    at::Tensor lg = lm_head(sel);
-    if (pg_ && !gather_logits) {
+    at::Tensor lg = logits_tail(x, rows);
+    if (!pg_) return lg;
+    if (!gather_logits) {
       // vocab-parallel sampling downstream: this rank's valid slice only
       const int64_t valid = std::max<int64_t>(0, std::min<int64_t>(lg.size(1), vocab_ - vocab_start_));
       return valid == lg.size(1) ? lg : lg.narrow(1, 0, valid);
     }
-    if (pg_) {
-      const int64_t world = pg_->getSize();
-      std::vector<at::Tensor> parts;
-      for (int64_t i = 0; i < world; ++i) parts.push_back(at::empty_like(lg));
-      std::vector<std::vector<at::Tensor>> outs{parts};
-      std::vector<at::Tensor> ins{lg.contiguous()};
-      pg_->allgather(outs, ins)->wait();
-      lg = at::cat(parts, 1);
-    }
-    if (lg.size(1) != vocab_) lg = lg.narrow(1, 0, vocab_).contiguous();
-    return lg;
+    const int64_t world = pg_->getSize();
+    std::vector<at::Tensor> parts;
+    for (int64_t i = 0; i < world; ++i) parts.push_back(at::empty_like(lg));
+    std::vector<std::vector<at::Tensor>> outs{parts};
+    std::vector<at::Tensor> ins{lg.contiguous()};
+    pg_->allgather(outs, ins)->wait();
+    return narrow_vocab(at::cat(parts, 1));
   }
 
   // Decode-only steps of 129..256 rows at TP = 1: the norm-deferred layer of
@@ -613,10 +444,7 @@ class LlamaRunner {
     }
     at::Tensor x = at::empty_like(h);
     rows_rms_scale(x, y, ss_in, eps_);
-    at::Tensor sel = rows.has_value() ? x.index_select(0, *rows) : x;
-    at::Tensor lg = lm_head(sel);
-    if (lg.size(1) != vocab_) lg = lg.narrow(1, 0, vocab_).contiguous();
-    return lg;
+    return logits_tail(x, rows);
   }
 
   at::Tensor forward(at::Tensor ids, at::Tensor pos, at::Tensor slots, int64_t num_decode,
@@ -664,10 +492,7 @@ class LlamaRunner {
   // (profiles/eng2_fused_r4.log) -- the 32 MB of slab writes + reads after the
   // rendezvous cost more than the reduce launches they replace.
   static bool fused_env() {
-    static const bool on = [] {
-      const char* e = getenv("LS_DGEMM_FUSED");
-      return e != nullptr && e[0] == '1';
-    }();
+    static const bool on = env_flag("LS_DGEMM_FUSED", false);
     return on;
   }
   bool fused_ready(int64_t T) const {
@@ -676,10 +501,7 @@ class LlamaRunner {
   }
 
   static bool gemv_enabled() {
-    static const bool on = [] {
-      const char* v = std::getenv("LS_GEMV");
-      return !(v && std::string(v) == "0");
-    }();
+    static const bool on = env_flag("LS_GEMV", true);
     return on;
   }
 
@@ -689,36 +511,24 @@ class LlamaRunner {
   // plain + a separate fused_add_rmsnorm launch; batch-4 decode step 4.59 -> 4.15 ms
   // (tools/gemv_bench.py, tools/engine_bench.py; profiles/gemv_r4/gemv_ab_r4h.log).
   static int gemv_pro_max_t() {
-    static const int t = [] {
-      const char* e = getenv("LS_GEMV_PRO_MAX_T");
-      return e ? atoi(e) : 2;
-    }();
+    static const int t = env_int("LS_GEMV_PRO_MAX_T", 2);
     return t;
   }
 
-  // LS_ATTN_ROPE=0: separate rope_cache launch before decode attention (A/B switch)
   // Decode-only steps whose qkv runs on the split-K decode GEMM: RoPE + the K/V cache
   // write inside its reduction (LS_QKV_ROPE=0: the attention kernel's fused form instead).
   static bool qkv_rope_fused() {
-    static const bool on = [] {
-      const char* e = getenv("LS_QKV_ROPE");
-      return e == nullptr || e[0] != '0';
-    }();
+    static const bool on = env_flag("LS_QKV_ROPE", true);
     return on;
   }
+  // LS_ATTN_ROPE=0: separate rope_cache launch before decode attention (A/B switch)
   static bool rope_fused() {
-    static const bool on = [] {
-      const char* e = getenv("LS_ATTN_ROPE");
-      return e == nullptr || e[0] != '0';
-    }();
+    static const bool on = env_flag("LS_ATTN_ROPE", true);
     return on;
   }
 
   static bool skinny_enabled() {
-    static const bool on = [] {
-      const char* e = getenv("LS_SKINNY_GEMM");
-      return e == nullptr || e[0] != '0';
-    }();
+    static const bool on = env_flag("LS_SKINNY_GEMM", true);
     return on;
   }
   // Prefill-sized steps (T >= LS_PGEMM_MIN_T, default 1024) run all four projections on
@@ -734,6 +544,15 @@ class LlamaRunner {
   // 0: not a prefill-sized step (decode GEMM blocks / library below), 1: gemm_prefill,
   // 2: the library GEMM (route mode, where the table measured it faster)
   static int prefill_route(int64_t T, const at::Tensor& w, bool silu) {
+    static const int64_t min_t = env_int("LS_PGEMM_MIN_T", 1024);
+    const int mode = pgemm_mode();
+    if (mode == 0 || !gemm_prefill_supported(w, silu) || T < min_t) return 0;
+    if (silu || mode == 2) return 1;
+    return pgemm_route::use_pp(T, w.size(0), w.size(1)) ? 1 : 2;
+  }
+  // LS_PGEMM, a word knob parsed here only: 0 "lib" / "0" (the library GEMM), 1 "route" /
+  // "1" (by the table), 2 unset or anything else (all hand-written)
+  static int pgemm_mode() {
     static const int mode = [] {
       const char* e = getenv("LS_PGEMM");
       if (e == nullptr) return 2;
@@ -742,21 +561,17 @@ class LlamaRunner {
       if (v == "route" || v == "1") return 1;
       return 2;
     }();
-    static const int64_t min_t = [] {
-      const char* e = getenv("LS_PGEMM_MIN_T");
-      return e ? (int64_t)atoll(e) : (int64_t)1024;
-    }();
-    if (mode == 0 || !gemm_prefill_supported(w, silu) || T < min_t) return 0;
-    if (silu || mode == 2) return 1;
-    return pgemm_route::use_pp(T, w.size(0), w.size(1)) ? 1 : 2;
+    return mode;
   }
   // rows below the prefill threshold: the decode GEMM in 256-row blocks
   bool dgemm_blocks_ok(const at::Tensor& w, bool silu) const {
-    static const bool lib = [] {
-      const char* e = getenv("LS_PGEMM");
-      return e != nullptr && (std::string(e) == "lib" || std::string(e) == "0");
-    }();
-    return !lib && dgemm_enabled() && dg_ws_.defined() && decode_gemm_supported(w, silu);
+    return pgemm_mode() != 0 && dgemm_enabled() && dg_ws_.defined() && decode_gemm_supported(w, silu);
+  }
+  // call(r0, n) for each block [r0, r0 + n) of at most kDgemmMaxM of T rows: the decode
+  // GEMM entry points take one 256-row tile per call
+  template <typename F>
+  static void dgemm_blocks(int64_t T, F&& call) {
+    for (int64_t r0 = 0; r0 < T; r0 += kDgemmMaxM) call(r0, std::min<int64_t>(kDgemmMaxM, T - r0));
   }
   // Fallback routing when the decode GEMM does not take a step (LS_DGEMM=0, or T below
   // LS_DGEMM_MIN_T): qkv rows up to this many go to the skinny ring.  With the default
@@ -764,10 +579,7 @@ class LlamaRunner {
   // faster than the skinny ring at every M from 5, profiles/dgemm_smallm_r4.log), so this
   // knob only matters for those A/B runs.
   static int64_t skinny_qkv_max() {
-    static const int64_t v = [] {
-      const char* e = getenv("LS_SKINNY_QKV_MAX");
-      return e ? (int64_t)atoll(e) : (int64_t)32;
-    }();
+    static const int64_t v = env_int("LS_SKINNY_QKV_MAX", 32);
     return v;
   }
   static bool skinny_shape(const at::Tensor& w) { return w.size(0) % 128 == 0 && w.size(1) % 64 == 0; }
@@ -777,10 +589,7 @@ class LlamaRunner {
   // skinny ring.  LS_DGEMM=0 turns it off (A/B switch).
   static constexpr int64_t kDgemmMaxM = 256;
   static bool dgemm_enabled() {
-    static const bool on = [] {
-      const char* e = getenv("LS_DGEMM");
-      return e == nullptr || e[0] != '0';
-    }();
+    static const bool on = env_flag("LS_DGEMM", true);
     return on;
   }
   // From 5 rows (the GEMV takes 1..4): measured against hipBLASLt and the skinny ring at
@@ -788,23 +597,68 @@ class LlamaRunner {
   // vs 28.8-31.1 (hipBLASLt) / 18.3-27.5 (skinny), gate_up + SwiGLU 52.4-54.3 vs
   // 53.8-62.7 / 57.7-59.3, down 30.5-37.8 vs 34.3-84.0 / 35.0-45.4.
   static int64_t dgemm_min_t() {
-    static const int64_t min_t = [] {
-      const char* e = getenv("LS_DGEMM_MIN_T");
-      return e ? (int64_t)atoll(e) : (int64_t)5;
-    }();
+    static const int64_t min_t = env_int("LS_DGEMM_MIN_T", 5);
     return min_t;
   }
   // the norm-deferred layer from this many rows (LS_DGEMM_FUSED_MIN_T)
   static int64_t fused_min_t() {
-    static const int64_t v = [] {
-      const char* e = getenv("LS_DGEMM_FUSED_MIN_T");
-      return e ? (int64_t)atoll(e) : (int64_t)129;
-    }();
+    static const int64_t v = env_int("LS_DGEMM_FUSED_MIN_T", 129);
     return v;
   }
   bool dgemm(int64_t T, const at::Tensor& w, bool silu) const {
     return dgemm_enabled() && dg_ws_.defined() && T >= dgemm_min_t() && T <= kDgemmMaxM &&
            decode_gemm_supported(w, silu);
+  }
+
+  // Row-parallel projection (o_proj, down_proj) with the residual add + RMSNorm that
+  // follows it: returns rmsnorm(residual += x . w^T) * norm_w, residual updated in place.
+  // Kernel by row count: the GEMV (gv), the decode GEMM, the skinny ring for T in
+  // [sk_min, sk_max], else proj().  At TP = 1 the decode GEMM and the skinny ring fuse the
+  // add + norm into their split-K reduction; under TP they store the plain GEMM, the
+  // partial sums are all-reduced, and the add + norm runs after (as for the GEMV and
+  // proj(), which fuse nothing).
+  at::Tensor row_proj(const at::Tensor& x, const at::Tensor& w, const at::Tensor& residual, const at::Tensor& norm_w,
+                      bool gv, int64_t sk_min, int64_t sk_max) {
+    const int64_t T = x.size(0);
+    at::Tensor out;
+    bool normed = false;
+    if (gv && gemv_supported(w, false)) {
+      out = at::empty_like(residual);
+      gemv(out, x, w);
+    } else if (dgemm(T, w, false)) {
+      out = at::empty_like(residual);
+      if (!pg_) {
+        decode_gemm(out, x, w, dg_ws_, residual, norm_w, eps_, 0, 0);
+        normed = true;
+      } else {
+        decode_gemm(out, x, w, dg_ws_, c10::nullopt, c10::nullopt, eps_, 0, 0);
+      }
+    } else if (skinny_enabled() && T >= sk_min && T <= sk_max && skinny_shape(w)) {
+      out = at::empty_like(residual);
+      if (!pg_) {
+        skinny_gemm_add_rmsnorm(out, x, w, residual, norm_w, eps_);
+        normed = true;
+      } else {
+        skinny_gemm(out, x, w);
+      }
+    } else {
+      out = proj(x, w);
+    }
+    if (!normed) {
+      all_reduce(out);
+      fused_add_rmsnorm(out, residual, norm_w, eps_);
+    }
+    return out;
+  }
+
+  at::Tensor narrow_vocab(const at::Tensor& lg) const {
+    return lg.size(1) != vocab_ ? lg.narrow(1, 0, vocab_).contiguous() : lg;
+  }
+  // f32 logits of the selected rows (all when `rows` is empty).  Under TP this is the
+  // rank's vocabulary shard, which forward_impl slices or gathers.
+  at::Tensor logits_tail(const at::Tensor& x, const c10::optional<at::Tensor>& rows) {
+    at::Tensor lg = lm_head(rows.has_value() ? x.index_select(0, *rows) : x);
+    return pg_ ? lg : narrow_vocab(lg);
   }
 
   void all_reduce(at::Tensor& t) {
@@ -1024,7 +878,7 @@ class StepExecutor {
     // tools/gap_analysis.py), so a launch issued from the engine thread came only after
     // the engine's own bookkeeping for the previous step -- the GPU idled ~0.5 ms per step
     // in the RAG pipeline.  A dedicated thread keeps the next step's launch queued.
-    static const bool async_env = getenv("LS_ASYNC_LAUNCH") ? atoi(getenv("LS_ASYNC_LAUNCH")) != 0 : true;
+    static const bool async_env = env_flag("LS_ASYNC_LAUNCH", true);
     if (!r_->pg() && async_env) {
       stream_ = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
       launcher_ = std::thread([this] { launcher_loop(); });

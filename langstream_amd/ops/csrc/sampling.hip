@@ -22,7 +22,7 @@
 // (sparse triples; host builds them only for rows that use penalties / logit_bias).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "ops.h"
 
 namespace {
 

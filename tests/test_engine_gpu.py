@@ -427,9 +427,12 @@ def test_native_executor_tp2_two_ranks_one_gpu(oneshot, graphs):
 
 
 def test_norm_deferred_decode_layer_matches_python_executor():
-    """Decode batches of 129..256 rows run the norm-deferred layer (LlamaRunner::
-    forward_dgemm: in-launch split-K combines, 1/rms in the consumer epilogues): greedy
-    tokens against the Python executor's op-by-op path over 160 concurrent sequences."""
+    """Decode batches of 129..256 rows: greedy tokens against the Python executor's
+    op-by-op path over 160 concurrent sequences.  With LS_DGEMM_FUSED off (the default)
+    these steps run LlamaRunner::forward_impl's main loop on the 256-row decode GEMMs
+    (qkv with RoPE + the KV write in its split-K reduction, o / down with the residual
+    add + RMSNorm in theirs, gate_up with the SwiGLU epilogue); only a process started
+    with LS_DGEMM_FUSED=1 runs the norm-deferred layer (forward_dgemm) here."""
     from langstream_amd.engine.arena import PyStepExecutor
     from langstream_amd.engine.llm_engine import NSLOTS
     cfg = PRESETS["llama-small"]
