@@ -323,7 +323,11 @@ RESOURCE_MODELS: Dict[str, Model] = {
     "local-gpu-configuration": Model("Local GPU engine", "In-process MI355X engines (Llama decode + embeddings).", {
         "model": S("Chat/completion model config name."), "embeddings-model": S("Embedding model config name."),
         "checkpoint": S("Safetensors checkpoint directory."), "tp": I("Tensor-parallel degree."),
-        "max-batch": I("Max concurrent sequences."), "max-seq-len": I("Max sequence length.")},
+        "max-batch": I("Max concurrent sequences."), "max-seq-len": I("Max sequence length."),
+        "kv-cache-dtype": S("Paged KV cache element type: auto (the model dtype), bf16 or fp8 (e4m3, twice the "
+                            "tokens per kv-fraction); unset: the LS_KV_CACHE_DTYPE environment variable, else auto."),
+        "kv-k-scale": N("fp8 KV cache: K is stored as K / kv-k-scale.", default=1.0),
+        "kv-v-scale": N("fp8 KV cache: V is stored as V / kv-v-scale.", default=1.0)},
         allow_unknown=True),
 }
 DATASOURCE_MODELS: Dict[str, Model] = {

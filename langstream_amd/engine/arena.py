@@ -189,6 +189,8 @@ class PyStepExecutor:
             src = torch.from_numpy(a["kvcopy"][:nc, 0].astype(np.int64)).to(self.device)
             dst = torch.from_numpy(a["kvcopy"][:nc, 1].astype(np.int64)).to(self.device)
             for kc, vc in self.kv:
+                if kc.element_size() == 1:   # fp8 cache: whole blocks move as bytes
+                    kc, vc = kc.view(torch.uint8), vc.view(torch.uint8)
                 kc[dst] = kc[src]
                 vc[dst] = vc[src]
         T, nd, nps, ntiles, nrows = (int(h[i]) for i in (H_T, H_ND, H_NPS, H_NTILES, H_NROWS))

@@ -167,7 +167,8 @@ class LLMEngine:
     def __init__(self, model: LlamaModel, tokenizer=None, *, num_blocks: Optional[int] = None,
                  kv_fraction: float = 0.55, max_model_len: int = 4096, max_batch: int = 256,
                  max_prefill_tokens: int = 8192, use_graphs: bool = True, graph_buckets: Sequence[int] = (),
-                 lookahead: bool = True, device=None, prefix_cache: Optional[bool] = None):
+                 lookahead: bool = True, device=None, prefix_cache: Optional[bool] = None,
+                 kv_cache_dtype: str = "auto", kv_k_scale: float = 1.0, kv_v_scale: float = 1.0):
         self.model = model
         self.cfg = model.cfg
         self.tok = tokenizer
@@ -184,7 +185,21 @@ class LLMEngine:
         self.lookahead = lookahead
         D = self.cfg.head_dim
         hkv = model.hkv
-        bytes_per_block = 2 * self.cfg.num_layers * hkv * BLOCK * D * torch.finfo(model.dtype).bits // 8
+        # KV cache element type: "auto" is the model dtype (bf16 on the GPU), "bf16" asks for
+        # it by name, "fp8" stores e4m3 codes (ops.reference.quantize_kv) with one K and one
+        # V scale for the whole engine
+        kvd = str(kv_cache_dtype).lower()
+        if kvd not in ("auto", "bf16", "fp8"):
+            raise ValueError(f"kv_cache_dtype must be auto, bf16 or fp8, not {kv_cache_dtype!r}")
+        if kvd == "fp8" and not (kv_k_scale > 0 and kv_v_scale > 0):
+            raise ValueError("kv_k_scale and kv_v_scale must be positive")
+        self.kv_dtype = {"fp8": ops.ref.FP8_DTYPE, "bf16": torch.bfloat16}.get(kvd, model.dtype)
+        self.kv_cache_dtype = {ops.ref.FP8_DTYPE: "fp8", torch.bfloat16: "bf16"}.get(
+            self.kv_dtype, str(self.kv_dtype).replace("torch.", ""))
+        self.kv_k_scale, self.kv_v_scale = (float(kv_k_scale), float(kv_v_scale)) if kvd == "fp8" else (1.0, 1.0)
+        model.kv_k_scale, model.kv_v_scale = self.kv_k_scale, self.kv_v_scale
+        bytes_per_block = 2 * self.cfg.num_layers * hkv * BLOCK * D * torch.finfo(self.kv_dtype).bits // 8
+        self.kv_bytes_per_block = bytes_per_block
         if num_blocks is None:
             if self.is_gpu:
                 free, _ = torch.cuda.mem_get_info(self.device)
@@ -198,7 +213,7 @@ class LLMEngine:
         self.num_blocks = int(num_blocks)
         self.kv_caches = []
         for _ in range(self.cfg.num_layers):
-            self.kv_caches.append(ops.new_kv_cache(self.num_blocks, hkv, D, self.device, model.dtype))
+            self.kv_caches.append(ops.new_kv_cache(self.num_blocks, hkv, D, self.device, self.kv_dtype))
         self.allocator = lib().BlockAllocator(self.num_blocks)
         self.nsplit, self.bps = ops.decode_splits(self.max_blocks_per_seq)
         if prefix_cache is None:
@@ -231,7 +246,8 @@ class LLMEngine:
         self.stats = {"prefill_steps": 0, "decode_steps": 0, "mixed_steps": 0, "prefill_tokens": 0,
                       "decode_tokens": 0, "preemptions": 0, "requests": 0, "finished": 0, "graph_steps": 0,
                       "host_ms": 0.0, "wait_ms": 0.0, "launch_ms": 0.0, "retire_ms": 0.0, "prefix_hit_tokens": 0,
-                      "prompt_tokens": 0}
+                      "prompt_tokens": 0, "kv_cache_dtype": self.kv_cache_dtype,
+                      "kv_bytes_per_block": self.kv_bytes_per_block}
         # prompt lengths of the most recent requests (decode attention cost follows the longest context)
         self.prompt_lens: collections.deque = collections.deque(maxlen=8192)
         # wall-clock (time.time) times at which requests reached the scheduler

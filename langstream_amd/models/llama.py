@@ -203,6 +203,9 @@ class LlamaModel:
         self.cos_sin = ref.rope_cos_sin(cfg.max_position, cfg.head_dim, cfg.rope_theta, cfg.rope_scaling,
                                         device=self.device)
         self.scale = 1.0 / math.sqrt(cfg.head_dim)
+        # scales of an fp8 KV cache (the engine that owns the caches sets them; bf16 caches ignore them)
+        self.kv_k_scale = 1.0
+        self.kv_v_scale = 1.0
 
     # ------------------------------------------------------------------ weights io
     def state_dict(self) -> dict:
@@ -241,24 +244,27 @@ class LlamaModel:
         residual = h
         x = ops.rmsnorm(h, self.layers[0].in_norm, eps)
         D = cfg.head_dim
+        ks, vs = self.kv_k_scale, self.kv_v_scale
         for li, layer in enumerate(self.layers):
             kc, vc = kv_caches[li]
             qkv = _linear(x, layer.qkv_w)
-            ops.rope_and_cache(qkv, meta.positions, self.cos_sin, meta.slots, kc, vc, self.hq, self.hkv)
+            ops.rope_and_cache(qkv, meta.positions, self.cos_sin, meta.slots, kc, vc, self.hq, self.hkv,
+                               k_scale=ks, v_scale=vs)
             q = qkv[:, : self.hq * D]
             nd = meta.num_decode
             if meta.num_prefill_tokens == 0:
                 attn = ops.paged_decode_attention(q, kc, vc, meta.d_block_tables, meta.d_ctx_lens, self.scale,
                                                   nsplit=meta.nsplit, blocks_per_split=meta.blocks_per_split,
-                                                  workspace=meta.workspace)
+                                                  workspace=meta.workspace, k_scale=ks, v_scale=vs)
             else:
                 attn = torch.empty(q.shape[0], self.hq * D, dtype=q.dtype, device=q.device)
                 if nd:
                     ops.paged_decode_attention(q[:nd], kc, vc, meta.d_block_tables, meta.d_ctx_lens, self.scale,
                                                out=attn[:nd], nsplit=meta.nsplit,
-                                               blocks_per_split=meta.blocks_per_split, workspace=meta.workspace)
+                                               blocks_per_split=meta.blocks_per_split, workspace=meta.workspace,
+                                               k_scale=ks, v_scale=vs)
                 ops.paged_prefill_attention(q, kc, vc, meta.p_block_tables, meta.q_start, meta.q_len, meta.ctx_len,
-                                            meta.tiles, self.hq, self.scale, out=attn)
+                                            meta.tiles, self.hq, self.scale, out=attn, k_scale=ks, v_scale=vs)
             o = _linear(attn, layer.o_w)
             self.tp.all_reduce(o)
             ops.fused_add_rmsnorm(o, residual, layer.post_norm, eps)
@@ -289,7 +295,8 @@ class LlamaModel:
             self.embed, [l.qkv_w for l in L], [l.o_w for l in L], [l.gate_up_w for l in L],
             [l.down_w for l in L], [l.in_norm for l in L], [l.post_norm for l in L], self.final_norm,
             self.lm_head, [kv[0] for kv in kv_caches], [kv[1] for kv in kv_caches], self.cos_sin, self.hq,
-            self.hkv, self.cfg.head_dim, self.cfg.rms_eps, self.scale, self.cfg.vocab_size, self.vocab_start, pg)
+            self.hkv, self.cfg.head_dim, self.cfg.rms_eps, self.scale, self.cfg.vocab_size, self.vocab_start, pg,
+            self.kv_k_scale, self.kv_v_scale)
         self._runner = (key, runner, kv_caches)
         return runner
 

@@ -25,12 +25,14 @@ import torch
 from . import reference as ref
 
 KV_BLOCK = 64
+FP8_DTYPE = ref.FP8_DTYPE   # the opt-in 8-bit KV cache element type (OCP e4m3fn)
 
 
 def new_kv_cache(num_blocks: int, hkv: int, head_dim: int, device, dtype, zeros: bool = True):
     """(K, V) paged caches of one layer: K [NB, Hkv, 64, D]; V^T in 8-key groups
     [NB, Hkv, 8, D, 8] (element (d, key) of a block at [key // 8, d, key % 8]; see
-    ops/csrc/common.h vt_off)."""
+    ops/csrc/common.h vt_off).  dtype: the model dtype, or FP8_DTYPE for an fp8 cache (same
+    element layout at 1 byte each; format in ops.reference.quantize_kv)."""
     mk = torch.zeros if zeros else torch.empty
     return (mk(num_blocks, hkv, KV_BLOCK, head_dim, device=device, dtype=dtype),
             mk(num_blocks, hkv, KV_BLOCK // 8, head_dim, 8, device=device, dtype=dtype))
@@ -233,11 +235,13 @@ def bias_gelu_(x: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------- rope / kv cache
-def rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq: int, Hkv: int, apply_rope: bool = True):
+def rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq: int, Hkv: int, apply_rope: bool = True,
+                   k_scale: float = 1.0, v_scale: float = 1.0):
+    """k_scale / v_scale: the scales of an fp8 cache (ignored by bf16 caches)."""
     if _gpu(qkv):
-        hip().rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope)
+        hip().rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope, k_scale, v_scale)
     else:
-        ref.rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope)
+        ref.rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope, k_scale, v_scale)
 
 
 # ---------------------------------------------------------------- attention
@@ -255,8 +259,10 @@ def decode_splits(max_blocks: int, min_blocks_per_split: int = 0) -> tuple[int, 
 
 
 def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale, out=None,
-                           nsplit: int = 1, blocks_per_split: int = 1 << 30, workspace=None):
-    """q: [B, Hq*D] (may be a strided view into the QKV buffer); returns [B, Hq*D]."""
+                           nsplit: int = 1, blocks_per_split: int = 1 << 30, workspace=None,
+                           k_scale: float = 1.0, v_scale: float = 1.0):
+    """q: [B, Hq*D] (may be a strided view into the QKV buffer); returns [B, Hq*D].
+    k_scale / v_scale: the scales of an fp8 cache (ignored by bf16 caches)."""
     B = ctx_lens.shape[0]
     D = k_cache.shape[3]
     Hq = q.shape[-1] // D if q.dim() == 2 else q.shape[1]
@@ -266,9 +272,10 @@ def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale, o
             assert workspace is not None and workspace.numel() >= B * Hq * nsplit * (D + 2)
         ws = workspace if workspace is not None else out.new_empty(0, dtype=torch.float32)
         hip().paged_decode_attention(out, q, k_cache, v_cache, block_tables, ctx_lens, scale, nsplit,
-                                     min(blocks_per_split, block_tables.shape[1]), ws)
+                                     min(blocks_per_split, block_tables.shape[1]), ws, k_scale, v_scale)
         return out
-    r = ref.paged_decode_attention(q.reshape(B, Hq, D), k_cache, v_cache, block_tables, ctx_lens, scale)
+    r = ref.paged_decode_attention(q.reshape(B, Hq, D), k_cache, v_cache, block_tables, ctx_lens, scale,
+                                   k_scale, v_scale)
     r = r.reshape(B, Hq * D)
     if out is not None:
         out.copy_(r)
@@ -337,15 +344,16 @@ def prefill_tiles_np(q_lens, G: int, prefix_lens, out=None):
 
 
 def paged_prefill_attention(q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, tiles, Hq, scale,
-                            out=None):
+                            out=None, k_scale: float = 1.0, v_scale: float = 1.0):
     T = q.shape[0]
     D = k_cache.shape[3]
     if _gpu(q):
         out = torch.empty(T, Hq * D, dtype=q.dtype, device=q.device) if out is None else out
         hip().paged_prefill_attention(out, q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, tiles,
-                                      Hq, scale)
+                                      Hq, scale, k_scale, v_scale)
         return out
-    r = ref.paged_prefill_attention(q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, Hq, scale)
+    r = ref.paged_prefill_attention(q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, Hq, scale,
+                                    k_scale, v_scale)
     if out is None:
         return r
     for s, n in zip(q_start.tolist(), q_len.tolist()):

@@ -83,12 +83,34 @@ struct RopeArgs {
   bf16* vc;
 };
 
-template <int D, int WPP, bool PIPE, bool ROPE, int AUX = 0>
+// F8: e4m3 caches (common.h "FP8 KV cache", non-ROPE form only).  K and V fragments load
+// at the same ELEMENT offsets through the same per-block descriptors, 8 bytes per lane
+// instead of 16 (the descriptor byte ranges halve with the element size, so tail keys
+// still read zeros), and are decoded to bf16x8 in registers right at the MFMA sites: Q and
+// P stay bf16, the arithmetic is that of the bf16 kernel over the dequantised cache.  The
+// host folds k_scale into scale_log2; v_scale multiplies the f32 accumulators once.
+// Measured (tools/attn_bench.py --ring 3 --kv-dtype fp8, profiles/r7/kv_fp8/): B = 256 ctx
+// 270..550 60.7 us against 76.5 us bf16, B = 64 ctx 2048 66.5 against 93.1 us.  Rejected:
+// two blocks per iteration (the bf16 kernel's bytes in flight per wave; 256 VGPRs, 3-6
+// spilled): 57.4 / 67.7 us alone, no gain in the engine.
+template <int D, int WPP, bool PIPE, bool ROPE, int AUX = 0, bool F8 = false>
 __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2, 2))) decode_attn_kernel(
     bf16* __restrict__ out, const bf16* __restrict__ q, int64_t q_stride, const bf16* __restrict__ kc,
     const bf16* __restrict__ vc, const int32_t* __restrict__ block_tables, int max_blocks,
     const int32_t* __restrict__ ctx_lens, int Hkv, int G, int NB, float scale_log2, int min_bps,
-    float* __restrict__ part_o, float* __restrict__ part_ml, RopeArgs ra) {
+    float* __restrict__ part_o, float* __restrict__ part_ml, RopeArgs ra, float v_scale) {
+  static_assert(!(F8 && ROPE), "the fused-RoPE form writes bf16 K/V");
+  constexpr int EB = F8 ? 1 : 2;  // bytes per cache element
+  using Frag = std::conditional_t<F8, uint2, uint4>;  // 8 cache elements
+  auto frag8 = [](Frag v) {
+    if constexpr (F8) return fp8_unpack8(v);
+    else return __builtin_bit_cast(bf16x8, v);
+  };
+  auto load8 = [](auto rs, int off, auto polc) {
+    constexpr int POL = decltype(polc)::value;
+    if constexpr (F8) return __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, POL));
+    else return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, POL));
+  };
   constexpr int KS = D / 32;  // k-steps over the head dim
   constexpr int DT = D / 16;  // 16-wide output tiles over the head dim
   constexpr int HALF = D / 2;
@@ -143,50 +165,49 @@ __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2
   // layer (the activations and split-K slabs stay cached; profiles/nt_r3c/).  Back-to-back
   // isolated calls over one pool re-read the same cache and measure nt slower, so
   // tools/attn_bench.py runs with a ring of pools.  LS_ATTN_NT=0 turns it off.
-  const int kbyte = 8 * h * 2;
+  const int kbyte = 8 * h * EB;
 
   // AUX 3 (LS_ATTN_NT=2, the default): the FIRST block of a sequence loaded with the
   // cached policy, for template-prefix blocks shared by every prompt (engine/
   // prefix_cache.py); see the launch site for the measurements behind the default.
-  auto issue_k_p = [&](int bi, uint4(&kf)[4][KS], auto polc) {
-    constexpr int POL = decltype(polc)::value;
+  auto issue_k_p = [&](int bi, Frag(&kf)[4][KS], auto polc) {
     const int blk = __builtin_amdgcn_readfirstlane(block_of(bi));
     const int lim = __builtin_amdgcn_readfirstlane(min(ctx - bi * BS, BS));   // valid keys here (>= 1)
     const int64_t boff = ((int64_t)blk * Hkv + kvh) * BS * D;
-    auto krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(kc + boff), 0, lim * D * 2, 0x00020000);
+    auto krs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char*>(reinterpret_cast<const char*>(kc) + boff * EB), 0, lim * D * EB, 0x00020000);
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
       const int key = 32 * (kt >> 1) + 8 * (i16 >> 2) + 4 * (kt & 1) + (i16 & 3);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
-        kf[kt][ks] = __builtin_bit_cast(
-            uint4, __builtin_amdgcn_raw_buffer_load_b128(krs, key * D * 2 + 64 * ks + kbyte, 0, POL));
+        kf[kt][ks] = load8(krs, key * D * EB + 32 * EB * ks + kbyte, polc);
     }
   };
-  auto issue_v_p = [&](int bi, uint4(&vf)[2][DT], auto polc) {
-    constexpr int POL = decltype(polc)::value;
+  auto issue_v_p = [&](int bi, Frag(&vf)[2][DT], auto polc) {
     const int blk = __builtin_amdgcn_readfirstlane(block_of(bi));
     const int lim = __builtin_amdgcn_readfirstlane(min(ctx - bi * BS, BS));
     const int64_t boff = ((int64_t)blk * Hkv + kvh) * BS * D;
-    auto vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(vc + boff), 0, BS * D * 2, 0x00020000);
+    auto vrs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char*>(reinterpret_cast<const char*>(vc) + boff * EB), 0, BS * D * EB, 0x00020000);
 #pragma unroll
     for (int kg = 0; kg < 2; ++kg) {
       const bool vok = 32 * kg + 8 * h < lim;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        const int off = (int)vt_off(16 * dt + i16, 32 * kg + 8 * h, D) * 2;
-        vf[kg][dt] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(vrs, vok ? off : OOB, 0, POL));
+        const int off = (int)vt_off(16 * dt + i16, 32 * kg + 8 * h, D) * EB;
+        vf[kg][dt] = load8(vrs, vok ? off : OOB, polc);
       }
     }
   };
   // AUX 3: nt loads except for a sequence's first block (cached)
   constexpr bool FIRST_CACHED = AUX == 3;
   constexpr int POLX = AUX == 3 ? 2 : AUX;
-  auto issue_k = [&](int bi, uint4(&kf)[4][KS]) {
+  auto issue_k = [&](int bi, Frag(&kf)[4][KS]) {
     if (FIRST_CACHED && bi == 0) issue_k_p(bi, kf, std::integral_constant<int, 0>());
     else issue_k_p(bi, kf, std::integral_constant<int, POLX>());
   };
-  auto issue_v = [&](int bi, uint4(&vf)[2][DT]) {
+  auto issue_v = [&](int bi, Frag(&vf)[2][DT]) {
     if (FIRST_CACHED && bi == 0) issue_v_p(bi, vf, std::integral_constant<int, 0>());
     else issue_v_p(bi, vf, std::integral_constant<int, POLX>());
   };
@@ -195,8 +216,8 @@ __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2
   // issued as soon as the scores of block i are computed (its K registers are free) and
   // its V loads right after O += V P (same registers, no extra VGPRs), so a wave keeps
   // streaming while it does the softmax and the PV products.
-  uint4 kf[4][KS];
-  uint4 vf[2][DT];
+  Frag kf[4][KS];
+  Frag vf[2][DT];
   if (PIPE && bstart + wid < bend) {
     issue_k(bstart + wid, kf);
     issue_v(bstart + wid, vf);
@@ -289,7 +310,7 @@ __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf[kt][ks]), qf[ks], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag8(kf[kt][ks]), qf[ks], acc, 0, 0, 0);
       s[kt] = acc;
     }
     // ---- online softmax (row = qrow = lane&15; this lane holds 16 of the 64 keys)
@@ -339,12 +360,16 @@ __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2
       }
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt)
-        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vf[kg][dt]), pf, o[dt], 0, 0, 0);
+        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag8(vf[kg][dt]), pf, o[dt], 0, 0, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
     if (PIPE && more) issue_v(bi + WPP, vf);
   }
 
+  if constexpr (F8) {
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) o[dt] *= v_scale;
+  }
   // o[dt][r] = O[qrow i16][d = 16dt + 4h + r]
   if constexpr (WPP == 1) {
     // one wave owns the (pair, split): write straight from the accumulators
@@ -469,7 +494,10 @@ int64_t decode_nsplit(int64_t B, int64_t Hkv, int64_t nsplit_max) {
 static void decode_attention_launch(at::Tensor& out, const at::Tensor& q, const at::Tensor& k_cache,
                                     const at::Tensor& v_cache, const at::Tensor& block_tables,
                                     const at::Tensor& ctx_lens, double scale, int64_t nsplit, int64_t min_bps,
-                                    const at::Tensor& workspace, const RopeArgs* ra) {
+                                    const at::Tensor& workspace, const RopeArgs* ra, double k_scale = 1.0,
+                                    double v_scale = 1.0) {
+  const bool f8 = kv_is_fp8(k_cache, v_cache, "paged_decode_attention");
+  TORCH_CHECK(!f8 || (k_scale > 0.0 && v_scale > 0.0), "KV cache scales must be positive");
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16);
   TORCH_CHECK(out.is_contiguous() && q.stride(-1) == 1);
   TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 5, "k_cache [NB, Hkv, 64, D], v_cache [NB, Hkv, 8, D, 8]");
@@ -517,14 +545,18 @@ static void decode_attention_launch(at::Tensor& out, const at::Tensor& q, const 
   const RopeArgs rargs = rope ? *ra : RopeArgs{};
   const int wpp = env_wpp == 1 || env_wpp == 4 ? env_wpp : ((int64_t)B * Hkv >= WAVE_SLOTS && ns == 1 ? 1 : 4);
   dim3 grid(B * Hkv, ns);
-  const float sl2 = (float)scale * LOG2E;
+  // fp8: the K scale folds into the softmax scale
+  const float sl2 = f8 ? (float)scale * (float)k_scale * LOG2E : (float)scale * LOG2E;
+  const float vs = f8 ? (float)v_scale : 1.f;
 #define LAUNCH_R(DD, W, P, R)                                                                                 \
   if (attn_nt == 2) LAUNCH_A(DD, W, P, R, 3); else if (attn_nt) LAUNCH_A(DD, W, P, R, 2); else LAUNCH_A(DD, W, P, R, 0)
 #define LAUNCH_A(DD, W, P, R, A)                                                                              \
-  decode_attn_kernel<DD, W, P, R, A><<<grid, 64 * W, 0, stream>>>(                                            \
+  if (f8) LAUNCH_F(DD, W, P, false, A, true); else LAUNCH_F(DD, W, P, R, A, false)
+#define LAUNCH_F(DD, W, P, R, A, F)                                                                           \
+  decode_attn_kernel<DD, W, P, R, A, F><<<grid, 64 * W, 0, stream>>>(                                         \
       (bf16*)out.data_ptr(), (const bf16*)q.data_ptr(), q_stride, (const bf16*)k_cache.data_ptr(),            \
       (const bf16*)v_cache.data_ptr(), block_tables.data_ptr<int32_t>(), (int)block_tables.size(1),          \
-      ctx_lens.data_ptr<int32_t>(), Hkv, G, (int)k_cache.size(0), sl2, (int)min_bps, po, pml, rargs)
+      ctx_lens.data_ptr<int32_t>(), Hkv, G, (int)k_cache.size(0), sl2, (int)min_bps, po, pml, rargs, vs)
 #define LAUNCH_P(DD, W, P) \
   if (rope) LAUNCH_R(DD, W, P, true); else LAUNCH_R(DD, W, P, false)
 #define LAUNCH_K(DD, W) \
@@ -543,14 +575,15 @@ static void decode_attention_launch(at::Tensor& out, const at::Tensor& q, const 
 #undef LAUNCH_P
 #undef LAUNCH_R
 #undef LAUNCH_A
+#undef LAUNCH_F
 #undef LAUNCH
 }
 
 void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
                             at::Tensor block_tables, at::Tensor ctx_lens, double scale, int64_t nsplit,
-                            int64_t min_bps, at::Tensor workspace) {
+                            int64_t min_bps, at::Tensor workspace, double k_scale, double v_scale) {
   decode_attention_launch(out, q, k_cache, v_cache, block_tables, ctx_lens, scale, nsplit, min_bps, workspace,
-                          nullptr);
+                          nullptr, k_scale, v_scale);
 }
 
 // Decode-only step with RoPE and the KV-cache write fused in (see RopeArgs above).
@@ -560,6 +593,7 @@ void paged_decode_attention_rope(at::Tensor out, at::Tensor qkv, at::Tensor pos,
                                  at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, at::Tensor block_tables,
                                  at::Tensor ctx_lens, double scale, int64_t nsplit, int64_t min_bps,
                                  at::Tensor workspace) {
+  kv_require_bf16(k_cache, v_cache, "paged_decode_attention_rope");
   TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 2 && qkv.stride(1) == 1, "qkv must be [B, (Hq + 2 Hkv) D]");
   const int64_t Hkv = k_cache.size(1), D = k_cache.size(3), B = ctx_lens.numel();
   TORCH_CHECK(qkv.size(0) == B && out.numel() % (B * D) == 0);

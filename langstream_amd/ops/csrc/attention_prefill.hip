@@ -44,11 +44,18 @@ struct SeqMeta {
   const int32_t* ctx_len;  // total keys visible (prefix + q_len)
 };
 
-template <int D, bool PAGED>
+// F8 (PAGED only): e4m3 caches (common.h "FP8 KV cache").  A thread loads the same chunks,
+// 8 bytes each, and store_tile decodes them into the same bf16 LDS image; everything after
+// store_tile is the bf16 kernel.  The host folds k_scale into scale_log2; v_scale
+// multiplies the f32 output once in the epilogue.
+template <int D, bool PAGED, bool F8 = false>
 __global__ void __launch_bounds__(256, 2) prefill_attn_kernel(
     bf16* __restrict__ out, const bf16* __restrict__ q, int64_t q_stride, const bf16* __restrict__ kc,
     const bf16* __restrict__ vc, const int32_t* __restrict__ block_tables, int max_blocks, int NB,
-    SeqMeta meta, const int32_t* __restrict__ tiles, int Hq, int Hkv, float scale_log2, int64_t out_stride) {
+    SeqMeta meta, const int32_t* __restrict__ tiles, int Hq, int Hkv, float scale_log2, int64_t out_stride,
+    float v_scale) {
+  static_assert(PAGED || !F8, "fp8 is a KV-cache format");
+  using Chunk = std::conditional_t<F8, uint2, uint4>;  // 8 cache elements
   constexpr int KS = D / 32;
   constexpr int DT = D / 16;
   constexpr int NCH = D / 8;           // 16-B chunks per K row
@@ -96,16 +103,27 @@ __global__ void __launch_bounds__(256, 2) prefill_attn_kernel(
     for (int dt = 0; dt < DT; ++dt) o[n][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m[2] = {-1e30f, -1e30f}, l[2] = {0.f, 0.f};
 
-  uint4 kreg[KPT], vreg[VPT];
+  Chunk kreg[KPT], vreg[VPT];
   auto load_tile = [&](int t) {
     if constexpr (PAGED) {
       const int blk = min(max(block_tables[(int64_t)seq * max_blocks + min(t, max_blocks - 1)], 0), NB - 1);
-      const bf16* kb = kc + ((int64_t)blk * Hkv + kvh) * KVT * D;
-      const bf16* vb = vc + ((int64_t)blk * Hkv + kvh) * D * KVT;
+      if constexpr (F8) {
+        const uint2* kb = reinterpret_cast<const uint2*>(reinterpret_cast<const fp8_t*>(kc) +
+                                                         ((int64_t)blk * Hkv + kvh) * KVT * D);
+        const uint2* vb = reinterpret_cast<const uint2*>(reinterpret_cast<const fp8_t*>(vc) +
+                                                         ((int64_t)blk * Hkv + kvh) * D * KVT);
 #pragma unroll
-      for (int i = 0; i < KPT; ++i) kreg[i] = ld16(kb + (threadIdx.x + 256 * i) * 8);
+        for (int i = 0; i < KPT; ++i) kreg[i] = kb[threadIdx.x + 256 * i];
 #pragma unroll
-      for (int i = 0; i < VPT; ++i) vreg[i] = ld16(vb + (threadIdx.x + 256 * i) * 8);
+        for (int i = 0; i < VPT; ++i) vreg[i] = vb[threadIdx.x + 256 * i];
+      } else {
+        const bf16* kb = kc + ((int64_t)blk * Hkv + kvh) * KVT * D;
+        const bf16* vb = vc + ((int64_t)blk * Hkv + kvh) * D * KVT;
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) kreg[i] = ld16(kb + (threadIdx.x + 256 * i) * 8);
+#pragma unroll
+        for (int i = 0; i < VPT; ++i) vreg[i] = ld16(vb + (threadIdx.x + 256 * i) * 8);
+      }
     } else {
       // K rows / V rows straight from the packed QKV tensor (keys beyond the sequence -> 0)
 #pragma unroll
@@ -124,25 +142,29 @@ __global__ void __launch_bounds__(256, 2) prefill_attn_kernel(
       }
     }
   };
+  auto chunk16 = [](Chunk v) {
+    if constexpr (F8) return __builtin_bit_cast(uint4, fp8_unpack8(v));
+    else return v;
+  };
   auto store_tile = [&]() {
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
       const int qi = threadIdx.x + 256 * i, key = qi / NCH, c = qi - key * NCH;
-      *reinterpret_cast<uint4*>(&ks_lds[key * D + 8 * (c ^ kswz<D>(key))]) = kreg[i];
+      *reinterpret_cast<uint4*>(&ks_lds[key * D + 8 * (c ^ kswz<D>(key))]) = chunk16(kreg[i]);
     }
     if constexpr (PAGED) {
       // source already V^T in 8-key groups: chunk qi = (key group c, dim d)
 #pragma unroll
       for (int i = 0; i < VPT; ++i) {
         const int qi = threadIdx.x + 256 * i, c = qi / D, d = qi - c * D;
-        *reinterpret_cast<uint4*>(&vs_lds[d * KVT + 8 * (c ^ vswz(d))]) = vreg[i];
+        *reinterpret_cast<uint4*>(&vs_lds[d * KVT + 8 * (c ^ vswz(d))]) = chunk16(vreg[i]);
       }
     } else {
       // source is V[key][d]: transpose while writing (2-B LDS stores)
 #pragma unroll
       for (int i = 0; i < VPT; ++i) {
         const int qi = threadIdx.x + 256 * i, key = qi / NCH, c = qi - key * NCH;
-        const bf16x8 v = __builtin_bit_cast(bf16x8, vreg[i]);
+        const bf16x8 v = __builtin_bit_cast(bf16x8, chunk16(vreg[i]));
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int d = c * 8 + j;
@@ -235,7 +257,8 @@ __global__ void __launch_bounds__(256, 2) prefill_attn_kernel(
     const int row = r0 + wid * 32 + n * 16 + i16;
     if (row < nrows) {
       const int tq = row / G, g = row - tq * G;
-      const float inv = l[n] > 0.f ? 1.f / l[n] : 0.f;
+      float inv = l[n] > 0.f ? 1.f / l[n] : 0.f;
+      if constexpr (F8) inv *= v_scale;
       bf16* op = out + (int64_t)(qs + tq) * out_stride + (int64_t)(kvh * G + g) * D + 4 * h;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
@@ -254,7 +277,9 @@ __global__ void __launch_bounds__(256, 2) prefill_attn_kernel(
 // tiles: [ntiles, 2] int32 (seq, first row) with rows = token*G + g, 128 rows per tile.
 void paged_prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
                              at::Tensor block_tables, at::Tensor q_start, at::Tensor q_len, at::Tensor ctx_len,
-                             at::Tensor tiles, int64_t Hq, double scale) {
+                             at::Tensor tiles, int64_t Hq, double scale, double k_scale, double v_scale) {
+  const bool f8 = kv_is_fp8(k_cache, v_cache, "paged_prefill_attention");
+  TORCH_CHECK(!f8 || (k_scale > 0.0 && v_scale > 0.0), "KV cache scales must be positive");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16 && q.stride(-1) == 1);
   TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(2) == KVT && v_cache.dim() == 5 && v_cache.size(2) == KVT / 8 &&
               v_cache.size(4) == 8, "KV block size must be 64 (v_cache [NB, Hkv, 8, D, 8])");
@@ -268,16 +293,21 @@ void paged_prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, a
   SeqMeta meta{q_start.data_ptr<int32_t>(), q_len.data_ptr<int32_t>(), ctx_len.data_ptr<int32_t>()};
   dim3 grid(ntiles, Hkv);
   auto stream = at::hip::getCurrentHIPStream();
-  const float sl2 = (float)scale * LOG2E_P;
-#define LAUNCH(DD)                                                                                                   \
-  prefill_attn_kernel<DD, true><<<grid, 256, 0, stream>>>(                                                          \
+  // fp8: the K scale folds into the softmax scale
+  const float sl2 = f8 ? (float)scale * (float)k_scale * LOG2E_P : (float)scale * LOG2E_P;
+  const float vs = f8 ? (float)v_scale : 1.f;
+#define LAUNCH_F(DD, FF)                                                                                             \
+  prefill_attn_kernel<DD, true, FF><<<grid, 256, 0, stream>>>(                                                      \
       (bf16*)out.data_ptr(), (const bf16*)q.data_ptr(), q.stride(0), (const bf16*)k_cache.data_ptr(),              \
       (const bf16*)v_cache.data_ptr(), block_tables.data_ptr<int32_t>(), (int)block_tables.size(1),                 \
-      (int)k_cache.size(0), meta, tiles.data_ptr<int32_t>(), (int)Hq, Hkv, sl2, out.stride(0))
-  if (D == 128) LAUNCH(128);
-  else if (D == 64) LAUNCH(64);
+      (int)k_cache.size(0), meta, tiles.data_ptr<int32_t>(), (int)Hq, Hkv, sl2, out.stride(0), vs)
+#define LAUNCH(DD) \
+  if (f8) LAUNCH_F(DD, true); else LAUNCH_F(DD, false)
+  if (D == 128) { LAUNCH(128); }
+  else if (D == 64) { LAUNCH(64); }
   else TORCH_CHECK(false, "unsupported head dim ", D);
 #undef LAUNCH
+#undef LAUNCH_F
 }
 
 // Dense bidirectional varlen attention over a packed QKV tensor [T, (Hq+2Hkv)*D]
@@ -299,7 +329,7 @@ void varlen_encoder_attention(at::Tensor out, at::Tensor qkv, at::Tensor q_start
   prefill_attn_kernel<DD, false><<<grid, 256, 0, stream>>>((bf16*)out.data_ptr(), base, qkv.stride(0),  \
                                                            base, base, nullptr, 1, 1, meta,             \
                                                            tiles.data_ptr<int32_t>(), (int)Hq, (int)Hkv, \
-                                                           sl2, out.stride(0))
+                                                           sl2, out.stride(0), 1.f)
   if (D == 32) LAUNCH(32);
   else if (D == 64) LAUNCH(64);
   else if (D == 128) LAUNCH(128);

@@ -86,6 +86,46 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
   return __builtin_bit_cast(uint4, b);
 }
 
+// ---------------------------------------------------------------------------------
+// FP8 KV cache (OCP e4m3fn, torch.float8_e4m3fn; 1 byte per element, same element
+// layout as the bf16 caches).  Stored code = e4m3(RNE(clamp(x * inv_scale, -448, 448)))
+// with x the bf16 value and inv_scale = 1 / scale an f32 computed once on the host.
+// The clamp makes the conversion saturating (+-Inf store +-448, never a NaN code).
+// Readers decode to bf16 (exact: e4m3 has 3 mantissa bits) and fold the scales into
+// the softmax scale (K) and the output (V); they never multiply per element.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned char fp8_t;
+
+__device__ __forceinline__ float fp8_prep(float x, float inv_scale) {
+  return fminf(fmaxf(x * inv_scale, -448.f), 448.f);
+}
+// 4 f32 -> 4 e4m3 codes (element i in byte i)
+__device__ __forceinline__ uint32_t fp8_pack4(float a, float b, float c, float d, float inv_scale) {
+  int p = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_prep(a, inv_scale), fp8_prep(b, inv_scale), 0, false);
+  p = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_prep(c, inv_scale), fp8_prep(d, inv_scale), p, true);
+  return (uint32_t)p;
+}
+__device__ __forceinline__ fp8_t fp8_from_bf16(bf16 x, float inv_scale) {
+  const float v = fp8_prep((float)x, inv_scale);
+  return (fp8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(v, v, 0, false) & 0xff);
+}
+// 8 bf16 (already rounded) -> 8 codes in one 8-byte word
+__device__ __forceinline__ uint2 fp8_pack8(bf16x8 v, float inv_scale) {
+  uint2 r;
+  r.x = fp8_pack4((float)v[0], (float)v[1], (float)v[2], (float)v[3], inv_scale);
+  r.y = fp8_pack4((float)v[4], (float)v[5], (float)v[6], (float)v[7], inv_scale);
+  return r;
+}
+// 8 codes -> bf16x8 (an MFMA operand), exact
+__device__ __forceinline__ bf16x8 fp8_unpack8(uint2 w) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w.x, 1.0f, false);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w.x, 1.0f, true);
+  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w.y, 1.0f, false);
+  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w.y, 1.0f, true);
+  return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
 // XCD-aware bijective remap of a linear workgroup id (guide §5 "XCD swizzle
 // must be bijective"): consecutive logical tiles land on the same XCD so they
 // share that XCD's L2.  Speed only -- never relied on for correctness.

@@ -810,12 +810,14 @@ void decode_gemm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspac
 // split-K reduce + the separate RoPE/cache pass (the attention then runs its un-fused
 // form: the fused-RoPE attention measured 91.6 vs 80.4 us at B = 256, ctx 410,
 // profiles/decode_attn_rope_isolated_r3.log).
-template <int D>
+// F8: e4m3 caches (common.h "FP8 KV cache"), codes from the bf16-rounded values of the row;
+// K as two 4-byte stores, V as 1-byte stores at an 8-byte stride.
+template <int D, bool F8>
 __global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(
     const float* __restrict__ part, int S, int M, int N, bf16* __restrict__ out, int64_t ldo,
     const int32_t* __restrict__ pos, const float* __restrict__ cos_sin, int max_pos,
     const int64_t* __restrict__ slots, int64_t nslots, bf16* __restrict__ kc, bf16* __restrict__ vc, int Hq, int Hkv,
-    int BS) {
+    int BS, float inv_k, float inv_v) {
   constexpr int HALF = D / 2, G4 = HALF / 4;
   const int H = Hq + 2 * Hkv;
   const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -869,15 +871,33 @@ __global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(
   if (sl < 0 || sl >= nslots) return;
   const int64_t blk = sl / BS, off = sl - blk * BS;
   if (hd < Hq + Hkv) {
-    bf16* kd = kc + ((blk * Hkv + (hd - Hq)) * BS + off) * D + 4 * c;
-    *reinterpret_cast<bf16x4*>(kd) = va;
-    *reinterpret_cast<bf16x4*>(kd + HALF) = vb;
+    const int64_t ko = ((blk * Hkv + (hd - Hq)) * BS + off) * D + 4 * c;
+    if constexpr (F8) {
+      fp8_t* kd = reinterpret_cast<fp8_t*>(kc) + ko;
+      *reinterpret_cast<uint32_t*>(kd) = fp8_pack4((float)va[0], (float)va[1], (float)va[2], (float)va[3], inv_k);
+      *reinterpret_cast<uint32_t*>(kd + HALF) =
+          fp8_pack4((float)vb[0], (float)vb[1], (float)vb[2], (float)vb[3], inv_k);
+    } else {
+      bf16* kd = kc + ko;
+      *reinterpret_cast<bf16x4*>(kd) = va;
+      *reinterpret_cast<bf16x4*>(kd + HALF) = vb;
+    }
   } else {
-    bf16* vd = vc + ((blk * Hkv + (hd - Hq - Hkv)) * (int64_t)D) * BS;
+    const int64_t vo = ((blk * Hkv + (hd - Hq - Hkv)) * (int64_t)D) * BS;
+    if constexpr (F8) {
+      fp8_t* vd = reinterpret_cast<fp8_t*>(vc) + vo;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      vd[vt_off(4 * c + j, (int)off, D)] = va[j];
-      vd[vt_off(HALF + 4 * c + j, (int)off, D)] = vb[j];
+      for (int j = 0; j < 4; ++j) {
+        vd[vt_off(4 * c + j, (int)off, D)] = fp8_from_bf16(va[j], inv_v);
+        vd[vt_off(HALF + 4 * c + j, (int)off, D)] = fp8_from_bf16(vb[j], inv_v);
+      }
+    } else {
+      bf16* vd = vc + vo;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        vd[vt_off(4 * c + j, (int)off, D)] = va[j];
+        vd[vt_off(HALF + 4 * c + j, (int)off, D)] = vb[j];
+      }
     }
   }
 }
@@ -886,8 +906,9 @@ __global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(
 // written to the paged cache (the same contract as decode_gemm + rope_and_cache).
 void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor pos,
                           at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, int64_t Hq,
-                          int64_t Hkv) {
+                          int64_t Hkv, double k_scale, double v_scale) {
   check_xw(x, w);
+  const bool f8 = kv_is_fp8(k_cache, v_cache, "decode_gemm_qkv_rope");
   const int M = (int)x.size(0), K = (int)x.size(1), N = (int)w.size(0);
   const int D = (int)k_cache.size(3), BSZ = (int)k_cache.size(2);
   TORCH_CHECK(N == (Hq + 2 * Hkv) * D && N % 128 == 0, "decode_gemm_qkv_rope: qkv width");
@@ -903,7 +924,7 @@ void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor
   const int S = std::min(4, pick_split(tiles, K, 4));
   if (S == 1 || D != 128) {
     decode_gemm(qkv, x, w, workspace, c10::nullopt, c10::nullopt, 1e-5, 0, 0);
-    rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, true);
+    rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, true, k_scale, v_scale);
     return;
   }
   TORCH_CHECK(workspace.scalar_type() == at::kFloat && workspace.numel() >= (int64_t)S * M * N,
@@ -915,10 +936,14 @@ void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor
   else
     dgemm_launch<128, EPI_PARTIAL>(S, tiles, st, x, w, M, N, K, nullptr, 0, part, 0, nullptr, nullptr, nullptr);
   const int64_t threads = (int64_t)M * (Hq + 2 * Hkv) * (D / 8);
-  splitk_reduce_rope_kernel<128><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(
-      part, S, M, N, (bf16*)qkv.data_ptr(), qkv.stride(0), pos.data_ptr<int32_t>(), cos_sin.data_ptr<float>(),
-      (int)cos_sin.size(0), slots.data_ptr<int64_t>(), k_cache.size(0) * BSZ, (bf16*)k_cache.data_ptr(),
-      (bf16*)v_cache.data_ptr(), (int)Hq, (int)Hkv, BSZ);
+  const float inv_k = kv_inv_scale(k_scale), inv_v = kv_inv_scale(v_scale);
+#define LAUNCH_RR(FF)                                                                                              \
+  splitk_reduce_rope_kernel<128, FF><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(                          \
+      part, S, M, N, (bf16*)qkv.data_ptr(), qkv.stride(0), pos.data_ptr<int32_t>(), cos_sin.data_ptr<float>(),    \
+      (int)cos_sin.size(0), slots.data_ptr<int64_t>(), k_cache.size(0) * BSZ, (bf16*)k_cache.data_ptr(),          \
+      (bf16*)v_cache.data_ptr(), (int)Hq, (int)Hkv, BSZ, inv_k, inv_v)
+  if (f8) LAUNCH_RR(true); else LAUNCH_RR(false);
+#undef LAUNCH_RR
 }
 
 // f32 OUTPUT (the LM head: logits the sampler reads in f32): out[M, N] f32 contiguous =
@@ -1079,6 +1104,7 @@ void decode_gemm_res(at::Tensor y_out, at::Tensor x, at::Tensor w, at::Tensor wo
 void decode_gemm_qkv_cmb(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor counters,
                          at::Tensor sumsq_in, double eps, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots,
                          at::Tensor k_cache, at::Tensor v_cache, int64_t Hq, int64_t Hkv, at::Tensor err) {
+  kv_require_bf16(k_cache, v_cache, "decode_gemm_qkv_cmb");
   const int M = (int)x.size(0), K = (int)x.size(1), N = (int)w.size(0);
   const int S = (int)decode_gemm_cmb_splits(N, K);
   check_cmb_common(x, w, workspace, counters, err, S);

@@ -472,8 +472,8 @@ QkvEpi make_qkv(const at::Tensor& out, const at::Tensor& pos, const at::Tensor& 
                 const at::Tensor& kc, const at::Tensor& vc, int64_t Hq, int64_t Hkv, bool apply_rope) {
   TORCH_CHECK(pos.scalar_type() == at::kInt && slots.scalar_type() == at::kLong && cos_sin.scalar_type() == at::kFloat &&
                   cos_sin.is_contiguous(), "gemv_qkv: pos int32, slots int64, cos_sin f32");
-  TORCH_CHECK(kc.dim() == 4 && vc.dim() == 5 && kc.scalar_type() == at::kBFloat16 && vc.scalar_type() == at::kBFloat16,
-              "gemv_qkv: paged caches [NB, Hkv, BS, D] / [NB, Hkv, BS/8, D, 8] bf16");
+  kv_require_bf16(kc, vc, "gemv_qkv");
+  TORCH_CHECK(kc.dim() == 4 && vc.dim() == 5, "gemv_qkv: paged caches [NB, Hkv, BS, D] / [NB, Hkv, BS/8, D, 8] bf16");
   const int D = kc.size(3), BS = kc.size(2);
   TORCH_CHECK(kc.size(1) == Hkv && vc.size(1) == Hkv && vc.size(2) == BS / 8 && vc.size(3) == D && vc.size(4) == 8 &&
                   cos_sin.size(1) == D, "gemv_qkv: cache / rope table shapes");

@@ -28,6 +28,27 @@ inline int64_t env_int(const char* name, int64_t dflt) {
 // plain call.
 inline bool env_flag(const char* name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; }
 
+// ------------------------------------------------------------------------ fp8 KV cache
+// The paged caches are bf16 or, opt-in, OCP e4m3 (torch.float8_e4m3fn; format in common.h).
+// True for an fp8 pair, false for a bf16 pair; anything else (mixed K / V included) raises.
+inline bool kv_is_fp8(const at::Tensor& k_cache, const at::Tensor& v_cache, const char* who) {
+  const auto kt = k_cache.scalar_type(), vt = v_cache.scalar_type();
+  TORCH_CHECK(kt == vt && (kt == at::kBFloat16 || kt == at::kFloat8_e4m3fn), who,
+              ": k_cache and v_cache must both be bf16 or both float8_e4m3fn");
+  return kt == at::kFloat8_e4m3fn;
+}
+// Entry points that write bf16 into the cache and have no fp8 form.
+inline void kv_require_bf16(const at::Tensor& k_cache, const at::Tensor& v_cache, const char* who) {
+  TORCH_CHECK(k_cache.scalar_type() == at::kBFloat16 && v_cache.scalar_type() == at::kBFloat16, who,
+              ": writes bf16 K/V and does not support an fp8 (float8_e4m3fn) KV cache; use rope_and_cache or "
+              "decode_gemm_qkv_rope for fp8 caches");
+}
+// 1 / scale, once, as the f32 every writer multiplies by.
+inline float kv_inv_scale(double scale) {
+  TORCH_CHECK(scale > 0.0, "KV cache scale must be positive");
+  return 1.0f / (float)scale;
+}
+
 // ---------------------------------------------------------------------------- norm.hip
 void rmsnorm(at::Tensor out, at::Tensor x, at::Tensor w, double eps);
 void fused_add_rmsnorm(at::Tensor x, at::Tensor residual, at::Tensor w, double eps);
@@ -42,12 +63,12 @@ void bias_gelu(at::Tensor x, c10::optional<at::Tensor> bias);
 
 // ---------------------------------------------------------------------------- rope.hip
 void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache,
-                    at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope);
+                    at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope, double k_scale, double v_scale);
 
 // ---------------------------------------------------------------- attention_decode.hip
 void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
                             at::Tensor block_tables, at::Tensor ctx_lens, double scale, int64_t nsplit,
-                            int64_t blocks_per_split, at::Tensor workspace);
+                            int64_t blocks_per_split, at::Tensor workspace, double k_scale, double v_scale);
 void paged_decode_attention_rope(at::Tensor out, at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin,
                                  at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, at::Tensor block_tables,
                                  at::Tensor ctx_lens, double scale, int64_t nsplit, int64_t min_bps,
@@ -56,7 +77,7 @@ void paged_decode_attention_rope(at::Tensor out, at::Tensor qkv, at::Tensor pos,
 // --------------------------------------------------------------- attention_prefill.hip
 void paged_prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
                              at::Tensor block_tables, at::Tensor q_start, at::Tensor q_len, at::Tensor ctx_len,
-                             at::Tensor tiles, int64_t Hq, double scale);
+                             at::Tensor tiles, int64_t Hq, double scale, double k_scale, double v_scale);
 void varlen_encoder_attention(at::Tensor out, at::Tensor qkv, at::Tensor q_start, at::Tensor q_len,
                               at::Tensor tiles, int64_t Hq, int64_t Hkv, double scale);
 
@@ -151,7 +172,7 @@ void decode_gemm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspac
                  c10::optional<at::Tensor> norm_w, double eps, int64_t bn_force, int64_t splits_force);
 void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor pos,
                           at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, int64_t Hq,
-                          int64_t Hkv);
+                          int64_t Hkv, double k_scale, double v_scale);
 bool decode_gemm_f32_supported(const at::Tensor& w, int64_t M);
 void decode_gemm_f32(at::Tensor out, at::Tensor x, at::Tensor w, int64_t bn_force);
 void decode_gemm_silu(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor tickets,

@@ -30,12 +30,16 @@ constexpr int TOK_SMALL = 2;
 constexpr int64_t SMALL_T = 2048;
 constexpr int HG = 8;    // heads per rotate workgroup
 
-template <int D, int TOK>
+// F8: e4m3 caches (common.h "FP8 KV cache"): the same element offsets at 1 byte each; K as
+// one 8-byte store per 8 rotated values, V as 1-byte stores at an 8-byte stride.  The codes
+// come from the bf16-rounded values the qkv row gets.
+template <int D, int TOK, bool F8>
 __global__ void __launch_bounds__(256) rope_cache_kernel(bf16* __restrict__ qkv, const int32_t* __restrict__ pos,
                                                          const float* __restrict__ cos_sin,
                                                          const int64_t* __restrict__ slots, bf16* __restrict__ kc,
                                                          bf16* __restrict__ vc, int64_t T, int Hq, int Hkv, int BS,
-                                                         int max_pos, int apply_rope, int64_t nslots) {
+                                                         int max_pos, int apply_rope, int64_t nslots, float inv_k,
+                                                         float inv_v) {
   constexpr int HALF = D / 2;
   constexpr int VPH = HALF / 8;  // 16-B vectors per half head
   const int64_t t0 = (int64_t)blockIdx.x * TOK;
@@ -81,9 +85,16 @@ __global__ void __launch_bounds__(256) rope_cache_kernel(bf16* __restrict__ qkv,
         const int64_t s = slots[t];
         if (s >= 0 && s < nslots) {
           const int64_t blk = s / BS, off = s - blk * BS;
-          bf16* kd = kc + ((blk * Hkv + (h - Hq)) * BS + off) * D;
-          st16(kd + c * 8, pa);
-          st16(kd + HALF + c * 8, pb);
+          const int64_t ko = ((blk * Hkv + (h - Hq)) * BS + off) * D;
+          if constexpr (F8) {
+            fp8_t* kd = reinterpret_cast<fp8_t*>(kc) + ko;
+            *reinterpret_cast<uint2*>(kd + c * 8) = fp8_pack8(__builtin_bit_cast(bf16x8, pa), inv_k);
+            *reinterpret_cast<uint2*>(kd + HALF + c * 8) = fp8_pack8(__builtin_bit_cast(bf16x8, pb), inv_k);
+          } else {
+            bf16* kd = kc + ko;
+            st16(kd + c * 8, pa);
+            st16(kd + HALF + c * 8, pb);
+          }
         }
       }
     }
@@ -99,18 +110,25 @@ __global__ void __launch_bounds__(256) rope_cache_kernel(bf16* __restrict__ qkv,
   if (s < 0 || s >= nslots) return;
   const int64_t blk = s / BS, off = s - blk * BS;
   const bf16* src = qkv + t * row_elems + (Hq + Hkv + hv) * D;
-  bf16* vd = vc + ((blk * Hkv + hv) * (int64_t)D) * BS;
-  for (int d = dr; d < D; d += 256 / TOK) vd[vt_off(d, (int)off, D)] = src[d];
+  const int64_t vo = ((blk * Hkv + hv) * (int64_t)D) * BS;
+  if constexpr (F8) {
+    fp8_t* vd = reinterpret_cast<fp8_t*>(vc) + vo;
+    for (int d = dr; d < D; d += 256 / TOK) vd[vt_off(d, (int)off, D)] = fp8_from_bf16(src[d], inv_v);
+  } else {
+    bf16* vd = vc + vo;
+    for (int d = dr; d < D; d += 256 / TOK) vd[vt_off(d, (int)off, D)] = src[d];
+  }
 }
 
 }  // namespace
 
 void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache,
-                    at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope) {
+                    at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope, double k_scale,
+                    double v_scale) {
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.is_contiguous());
   TORCH_CHECK(pos.scalar_type() == at::kInt && slots.scalar_type() == at::kLong);
   TORCH_CHECK(cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous());
-  TORCH_CHECK(k_cache.scalar_type() == at::kBFloat16 && v_cache.scalar_type() == at::kBFloat16);
+  const bool f8 = kv_is_fp8(k_cache, v_cache, "rope_and_cache");
   TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 5, "k_cache [NB, Hkv, BS, D], v_cache [NB, Hkv, BS/8, D, 8]");
   const int D = k_cache.size(3);
   const int BS = k_cache.size(2);
@@ -126,14 +144,17 @@ void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tens
   const bool small = T <= SMALL_T;
   const int tok = small ? TOK_SMALL : TOK_LARGE;
   dim3 grid((unsigned)((T + tok - 1) / tok), nq + nk + (int)Hkv);
-#define LAUNCH(DD, TT)                                                                                      \
-  rope_cache_kernel<DD, TT><<<grid, 256, 0, stream>>>((bf16*)qkv.data_ptr(), pos.data_ptr<int32_t>(),      \
-                                                      cos_sin.data_ptr<float>(), slots.data_ptr<int64_t>(), \
-                                                      (bf16*)k_cache.data_ptr(), (bf16*)v_cache.data_ptr(), T, \
-                                                      (int)Hq, (int)Hkv, BS, (int)cos_sin.size(0),          \
-                                                      apply_rope ? 1 : 0, (int64_t)k_cache.size(0) * BS)
-  if (D == 128) { if (small) LAUNCH(128, TOK_SMALL); else LAUNCH(128, TOK_LARGE); }
-  else if (D == 64) { if (small) LAUNCH(64, TOK_SMALL); else LAUNCH(64, TOK_LARGE); }
+  const float inv_k = kv_inv_scale(k_scale), inv_v = kv_inv_scale(v_scale);
+#define LAUNCH_F(DD, TT, FF)                                                                                \
+  rope_cache_kernel<DD, TT, FF><<<grid, 256, 0, stream>>>(                                                  \
+      (bf16*)qkv.data_ptr(), pos.data_ptr<int32_t>(), cos_sin.data_ptr<float>(), slots.data_ptr<int64_t>(), \
+      (bf16*)k_cache.data_ptr(), (bf16*)v_cache.data_ptr(), T, (int)Hq, (int)Hkv, BS, (int)cos_sin.size(0), \
+      apply_rope ? 1 : 0, (int64_t)k_cache.size(0) * BS, inv_k, inv_v)
+#define LAUNCH(DD, TT) \
+  if (f8) LAUNCH_F(DD, TT, true); else LAUNCH_F(DD, TT, false)
+  if (D == 128) { if (small) { LAUNCH(128, TOK_SMALL); } else { LAUNCH(128, TOK_LARGE); } }
+  else if (D == 64) { if (small) { LAUNCH(64, TOK_SMALL); } else { LAUNCH(64, TOK_LARGE); } }
   else TORCH_CHECK(false, "unsupported head dim ", D);
 #undef LAUNCH
+#undef LAUNCH_F
 }

@@ -95,15 +95,20 @@ class LlamaRunner {
               std::vector<at::Tensor> post_norm, at::Tensor final_norm, at::Tensor lm_head,
               std::vector<at::Tensor> k_caches, std::vector<at::Tensor> v_caches, at::Tensor cos_sin, int64_t hq,
               int64_t hkv, int64_t head_dim, double eps, double scale, int64_t vocab_size, int64_t vocab_start,
-              py::object process_group)
+              py::object process_group, double k_scale = 1.0, double v_scale = 1.0)
       : embed_(embed), qkv_w_(qkv_w), o_w_(o_w), gate_up_w_(gate_up_w), down_w_(down_w), in_norm_(in_norm),
         post_norm_(post_norm), final_norm_(final_norm), lm_head_(lm_head), kc_(k_caches), vc_(v_caches),
         cos_sin_(cos_sin), hq_(hq), hkv_(hkv), d_(head_dim), eps_(eps), scale_(scale), vocab_(vocab_size),
-        vocab_start_(vocab_start) {
+        vocab_start_(vocab_start), k_scale_(k_scale), v_scale_(v_scale) {
     const size_t L = qkv_w_.size();
     TORCH_CHECK(L > 0 && o_w_.size() == L && gate_up_w_.size() == L && down_w_.size() == L &&
                 in_norm_.size() == L && post_norm_.size() == L && kc_.size() == L && vc_.size() == L,
                 "inconsistent layer lists");
+    // fp8 (e4m3) KV caches: the mode follows the cache dtype, one dtype for every layer
+    f8_ = kv_is_fp8(kc_[0], vc_[0], "LlamaRunner");
+    for (size_t l = 1; l < L; ++l)
+      TORCH_CHECK(kv_is_fp8(kc_[l], vc_[l], "LlamaRunner") == f8_, "LlamaRunner: KV caches of one dtype");
+    TORCH_CHECK(k_scale > 0.0 && v_scale > 0.0, "LlamaRunner: KV cache scales must be positive");
     if (!process_group.is_none()) pg_ = py::cast<c10::intrusive_ptr<::c10d::ProcessGroup>>(process_group);
     // LS_ONESHOT_AR=1: decode-sized all-reduces (<= LS_ONESHOT_AR_MAX elements, default
     // 256 x 8192) through the one-shot IPC kernel (allreduce.hip) instead of RCCL.  Both
@@ -132,7 +137,7 @@ class LlamaRunner {
       }
       // the norm-deferred layer (forward_dgemm): combine-path splits must exist for qkv /
       // o / down, the head dim must be 128 (one head per 128-column tile)
-      bool fz = !pg_ && head_dim == 128 && fused_env();
+      bool fz = !pg_ && !f8_ && head_dim == 128 && fused_env();
       const int64_t H = embed_.size(1);
       for (size_t l = 0; l < L && fz; ++l) {
         const at::Tensor* ws[3] = {&qkv_w_[l], &o_w_[l], &down_w_[l]};
@@ -167,7 +172,12 @@ class LlamaRunner {
     if (n <= 0) return;
     if (!kv_tab_.defined()) {
       std::vector<int64_t> ptrs;
+      // the copy is byte-based: one block size for every K and V tensor, whatever the
+      // element type (bf16, or 1-byte fp8 codes)
+      const int64_t bb = kc_[0][0].numel() * kc_[0].element_size();
       for (size_t l = 0; l < kc_.size(); ++l) {
+        TORCH_CHECK(kc_[l][0].numel() * kc_[l].element_size() == bb && vc_[l][0].numel() * vc_[l].element_size() == bb,
+                    "KV caches: K and V blocks of one byte size in every layer");
         TORCH_CHECK(kc_[l].is_contiguous() && vc_[l].is_contiguous() && kc_[l].size(0) == kc_[0].size(0) &&
                     vc_[l].size(0) == kc_[0].size(0) && kc_[l][0].numel() == vc_[l][0].numel(),
                     "KV caches: contiguous, one block count, K and V blocks of one size");
@@ -175,7 +185,7 @@ class LlamaRunner {
         ptrs.push_back(reinterpret_cast<int64_t>(vc_[l].data_ptr()));
       }
       kv_tab_ = at::tensor(ptrs, at::TensorOptions().dtype(at::kLong)).to(embed_.device());
-      kv_block_bytes_ = kc_[0][0].numel() * kc_[0].element_size();
+      kv_block_bytes_ = bb;
       TORCH_CHECK(kv_block_bytes_ % 16 == 0);
     }
     kv_block_copy_kernel<<<dim3((unsigned)n, (unsigned)kv_tab_.numel()), 256, 0,
@@ -302,19 +312,20 @@ class LlamaRunner {
     // roped: RoPE + the K/V cache write already done by the qkv GEMM / GEMV
     auto attend = [&](int64_t l, const at::Tensor& qkv, bool roped) {
       at::Tensor attn = at::empty({T, hq_ * d_}, qkv.options());
-      if (!roped && decode_only && rope_fused()) {
+      if (!roped && decode_only && !f8_ && rope_fused()) {
         // decode-only step: RoPE + K/V cache write inside the attention kernel
         paged_decode_attention_rope(attn, qkv, pos, cos_sin_, slots, kc_[l], vc_[l], d_bt, d_ctx, scale_, nsplit,
                                     bps, ws);
         return attn;
       }
-      if (!roped) rope_and_cache(qkv, pos, cos_sin_, slots, kc_[l], vc_[l], hq_, hkv_, true);
+      if (!roped) rope_and_cache(qkv, pos, cos_sin_, slots, kc_[l], vc_[l], hq_, hkv_, true, k_scale_, v_scale_);
       at::Tensor q = qkv.narrow(1, 0, hq_ * d_);
       if (num_decode > 0)
         paged_decode_attention(attn.narrow(0, 0, num_decode), q.narrow(0, 0, num_decode), kc_[l], vc_[l], d_bt,
-                               d_ctx, scale_, nsplit, bps, ws);
+                               d_ctx, scale_, nsplit, bps, ws, k_scale_, v_scale_);
       if (num_prefill > 0)
-        paged_prefill_attention(attn, q, kc_[l], vc_[l], p_bt, q_start, q_len, ctx_len, tiles, hq_, scale_);
+        paged_prefill_attention(attn, q, kc_[l], vc_[l], p_bt, q_start, q_len, ctx_len, tiles, hq_, scale_, k_scale_,
+                                v_scale_);
       return attn;
     };
     // TP = 1: the residual add + RMSNorm after o_proj and down_proj run in the PROLOGUE of
@@ -322,7 +333,8 @@ class LlamaRunner {
     // from the L2-resident activations -- no separate norm kernels or hand-offs.  (A
     // last-block add+norm epilogue with an agent-scope ticket measured slower: 3.72 vs
     // 3.48 ms per batch-1 step, the serial tail outweighs the launch it saves.)
-    bool fused = gv && !pg_;
+    // (fp8 KV caches: the GEMV's qkv epilogue writes bf16 K/V, so the un-fused GEMVs below)
+    bool fused = gv && !pg_ && !f8_;
     for (int64_t l = 0; l < L && fused; ++l)
       fused = gemv_supported(qkv_w_[l], false) && gemv_supported(o_w_[l], false) &&
               gemv_supported(gate_up_w_[l], true) && gemv_supported(down_w_[l], false);
@@ -372,7 +384,8 @@ class LlamaRunner {
       } else if (dgemm(T, qkv_w_[l], false)) {
         qkv = at::empty({T, qkv_w_[l].size(0)}, x.options());
         if (decode_only && qkv_rope_fused()) {
-          decode_gemm_qkv_rope(qkv, x, qkv_w_[l], dg_ws_, pos, cos_sin_, slots, kc_[l], vc_[l], hq_, hkv_);
+          decode_gemm_qkv_rope(qkv, x, qkv_w_[l], dg_ws_, pos, cos_sin_, slots, kc_[l], vc_[l], hq_, hkv_, k_scale_,
+                               v_scale_);
           roped = true;
         } else {
           decode_gemm(qkv, x, qkv_w_[l], dg_ws_, c10::nullopt, c10::nullopt, eps_, 0, 0);
@@ -436,7 +449,8 @@ class LlamaRunner {
       decode_gemm_qkv_cmb(qkv, y, qkv_w_[l], dg_ws_, cnt_qkv_, l == 0 ? ss0 : ss_in, eps_, pos, cos_sin_, slots,
                           kc_[l], vc_[l], hq_, hkv_, err);
       at::Tensor attn = at::empty({T, hq_ * d_}, h.options());
-      paged_decode_attention(attn, qkv.narrow(1, 0, hq_ * d_), kc_[l], vc_[l], d_bt, d_ctx, scale_, nsplit, bps, ws);
+      paged_decode_attention(attn, qkv.narrow(1, 0, hq_ * d_), kc_[l], vc_[l], d_bt, d_ctx, scale_, nsplit, bps, ws,
+                             1.0, 1.0);
       decode_gemm_res(y2, attn, o_w_[l], dg_ws_, cnt_o_, h, post_norm_[l], ss_post, err);
       at::Tensor a = at::empty({T, gate_up_w_[l].size(0) / 2}, h.options());
       decode_gemm_silu_r(a, y2, gate_up_w_[l], ss_post, eps_);
@@ -687,6 +701,8 @@ class LlamaRunner {
   int64_t hq_, hkv_, d_;
   double eps_, scale_;
   int64_t vocab_, vocab_start_;
+  double k_scale_, v_scale_;   // fp8 KV cache scales (unused with bf16 caches)
+  bool f8_ = false;            // the KV caches are float8_e4m3fn
   c10::intrusive_ptr<::c10d::ProcessGroup> pg_;
 };
 
@@ -1308,7 +1324,12 @@ void bind_runners(py::module_& m) {
       .def(py::init<at::Tensor, std::vector<at::Tensor>, std::vector<at::Tensor>, std::vector<at::Tensor>,
                     std::vector<at::Tensor>, std::vector<at::Tensor>, std::vector<at::Tensor>, at::Tensor, at::Tensor,
                     std::vector<at::Tensor>, std::vector<at::Tensor>, at::Tensor, int64_t, int64_t, int64_t, double,
-                    double, int64_t, int64_t, py::object>())
+                    double, int64_t, int64_t, py::object, double, double>(),
+           py::arg("embed"), py::arg("qkv_w"), py::arg("o_w"), py::arg("gate_up_w"), py::arg("down_w"),
+           py::arg("in_norm"), py::arg("post_norm"), py::arg("final_norm"), py::arg("lm_head"), py::arg("k_caches"),
+           py::arg("v_caches"), py::arg("cos_sin"), py::arg("hq"), py::arg("hkv"), py::arg("head_dim"),
+           py::arg("eps"), py::arg("scale"), py::arg("vocab_size"), py::arg("vocab_start"),
+           py::arg("process_group"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0)
       .def("forward", &LlamaRunner::forward, py::call_guard<py::gil_scoped_release>());
   py::class_<BertRunner>(m, "BertRunner")
       .def(py::init<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<std::vector<at::Tensor>>,

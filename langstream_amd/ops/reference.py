@@ -12,6 +12,27 @@ import torch
 
 KV_BLOCK = 64
 
+# ---- fp8 paged KV cache (opt-in).  Element type OCP e4m3fn, the K / V layouts of the bf16
+# cache at 1 byte per element, and two per-engine f32 scalars k_scale / v_scale:
+#   stored code = e4m3(RNE(clamp(x * (1 / scale), -448, 448)))
+# with x the value a bf16 cache would hold and 1 / scale computed once as an f32.  The
+# conversion saturates (+-Inf store +-448; never a NaN code for a non-NaN input).  Readers
+# do not multiply per element: k_scale folds into the softmax scale, v_scale multiplies the
+# attention output once in f32.
+FP8_DTYPE = torch.float8_e4m3fn
+FP8_MAX = 448.0
+
+
+def is_fp8(t) -> bool:
+    return t.dtype == FP8_DTYPE
+
+
+def quantize_kv(x, scale: float = 1.0):
+    """The fp8 cache code of every element of x (any float dtype) -> float8_e4m3fn.  The
+    clamp comes first: torch's cast rounds to nearest even but returns NaN past 464."""
+    inv = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(scale), dtype=torch.float32)
+    return (x.float() * inv.to(x.device)).clamp(-FP8_MAX, FP8_MAX).to(FP8_DTYPE)
+
 
 def rmsnorm(x, w, eps):
     xf = x.float()
@@ -115,7 +136,10 @@ def apply_rope(x, pos, cos_sin):
     return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1).to(x.dtype)
 
 
-def rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope_flag=True):
+def rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope_flag=True, k_scale=1.0,
+                   v_scale=1.0):
+    assert k_cache.dtype == v_cache.dtype, "K and V caches of one dtype"
+    f8 = is_fp8(k_cache)
     T = qkv.shape[0]
     D = k_cache.shape[3]
     BS = k_cache.shape[2]
@@ -127,12 +151,16 @@ def rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_ro
         if s < 0:
             continue
         blk, off = divmod(s, BS)
-        k_cache[blk, :, off, :] = v[t, Hq: Hq + Hkv]
-        v_cache[blk, :, off // 8, :, off % 8] = v[t, Hq + Hkv:]    # [NB, Hkv, BS/8, D, 8]
+        kt, vt = v[t, Hq: Hq + Hkv], v[t, Hq + Hkv:]
+        if f8:   # codes of the (rotated, already rounded) row values
+            kt, vt = quantize_kv(kt, k_scale), quantize_kv(vt, v_scale)
+        k_cache[blk, :, off, :] = kt
+        v_cache[blk, :, off // 8, :, off % 8] = vt    # [NB, Hkv, BS/8, D, 8]
 
 
 def gather_kv(k_cache, v_cache, block_table, n):
-    """Contiguous K [n, Hkv, D] and V [n, Hkv, D] of one sequence from the paged cache."""
+    """Contiguous K [n, Hkv, D] and V [n, Hkv, D] of one sequence from the paged cache (in
+    the cache dtype: fp8 codes come back as codes, see dequant_kv)."""
     BS = k_cache.shape[2]
     nb = (n + BS - 1) // BS
     ks = [k_cache[int(block_table[i])] for i in range(nb)]           # [Hkv, BS, D]
@@ -140,6 +168,16 @@ def gather_kv(k_cache, v_cache, block_table, n):
     vs = [v_cache[int(block_table[i])].permute(0, 1, 3, 2).reshape(v_cache.shape[1], BS, -1) for i in range(nb)]
     K = torch.cat(ks, dim=1)[:, :n].transpose(0, 1)
     V = torch.cat(vs, dim=1)[:, :n].transpose(0, 1)
+    return K, V
+
+
+def dequant_kv(K, V, k_scale=1.0, v_scale=1.0):
+    """gather_kv's result as the values attention sees: fp8 codes -> f32 * scale; other
+    dtypes pass through (their scales are ignored)."""
+    if is_fp8(K):
+        K = K.float() * float(k_scale)
+    if is_fp8(V):
+        V = V.float() * float(v_scale)
     return K, V
 
 
@@ -159,7 +197,7 @@ def attention(q, k, v, scale, causal_offset: int | None):
     return torch.einsum("hqk,khd->qhd", p, vf).to(q.dtype)
 
 
-def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale):
+def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale, k_scale=1.0, v_scale=1.0):
     B = q.shape[0]
     D = k_cache.shape[3]
     qv = q.reshape(B, -1, D)
@@ -169,18 +207,19 @@ def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale):
         if n == 0:
             outs.append(torch.zeros_like(qv[b: b + 1]))
             continue
-        K, V = gather_kv(k_cache, v_cache, block_tables[b], n)
+        K, V = dequant_kv(*gather_kv(k_cache, v_cache, block_tables[b], n), k_scale, v_scale)
         outs.append(attention(qv[b: b + 1], K, V, scale, causal_offset=None))
     return torch.cat(outs, 0)
 
 
-def paged_prefill_attention(q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, Hq, scale):
+def paged_prefill_attention(q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, Hq, scale, k_scale=1.0,
+                            v_scale=1.0):
     D = k_cache.shape[3]
     T = q.shape[0]
     out = torch.empty(T, Hq, D, dtype=q.dtype, device=q.device)
     for s in range(len(q_start)):
         qs, ql, cl = int(q_start[s]), int(q_len[s]), int(ctx_len[s])
-        K, V = gather_kv(k_cache, v_cache, block_tables[s], cl)
+        K, V = dequant_kv(*gather_kv(k_cache, v_cache, block_tables[s], cl), k_scale, v_scale)
         qq = q[qs: qs + ql, : Hq * D].reshape(ql, Hq, D)
         out[qs: qs + ql] = attention(qq, K, V, scale, causal_offset=cl - ql)
     return out.reshape(T, Hq * D)

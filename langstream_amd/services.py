@@ -16,6 +16,8 @@ example applications run unmodified; hosted model names map through ``MODEL_ALIA
 Configuration (``local-gpu-configuration`` resource):
   chat-model (llama-3-8b), embeddings-model (bge-small-en), device, max-batch (256),
   max-model-len (4096), max-prefill-tokens (16384), kv-fraction (0.55), use-graphs (true),
+  kv-cache-dtype (auto | bf16 | fp8; unset: the LS_KV_CACHE_DTYPE environment variable, else auto),
+  kv-k-scale / kv-v-scale (1.0; the two scalars of an fp8 KV cache),
   weights-path / embeddings-weights-path (optional safetensors with our packed layout).
 """
 from __future__ import annotations
@@ -146,7 +148,10 @@ class ServiceRegistry:
                             max_prefill_tokens=int(c.get("max-prefill-tokens", 16384)),
                             kv_fraction=float(c.get("kv-fraction", 0.55)),
                             use_graphs=str(c.get("use-graphs", "true")).lower() == "true",
-                            num_blocks=c.get("num-blocks"))
+                            num_blocks=c.get("num-blocks"),
+                            kv_cache_dtype=str(c.get("kv-cache-dtype") or os.environ.get("LS_KV_CACHE_DTYPE")
+                                               or "auto"),
+                            kv_k_scale=float(c.get("kv-k-scale", 1.0)), kv_v_scale=float(c.get("kv-v-scale", 1.0)))
             if eng.use_graphs and str(c.get("capture-graphs", "true")).lower() == "true":
                 eng.capture_graphs()   # TP: every rank captures in lock-step
             if self.tp is None or self.tp.rank == 0:

@@ -1,6 +1,6 @@
 """Decode-attention timing over (batch, context) shapes + a correctness spot check.
 
-usage (GPU box): python tools/attn_bench.py [--shapes 256x448,64x2048,8x4000]
+usage (GPU box): python tools/attn_bench.py [--shapes 256x448,64x2048,8x4000] [--kv-dtype bf16|fp8]
 
 """
 from __future__ import annotations
@@ -63,9 +63,15 @@ def main():
     ap.add_argument("--rope", action="store_true",
                     help="time the decode-only variant with RoPE + the KV write fused in "
                          "(paged_decode_attention_rope over an un-rotated qkv buffer, as the engine runs it)")
+    ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
+                    help="KV cache element type: fp8 = e4m3 codes of the same randn values (1 byte per element)")
     a = ap.parse_args()
     Hq, Hkv, D = 32, 8, 128
     dev, bf = "cuda", torch.bfloat16
+    f8 = a.kv_dtype == "fp8"
+    assert not (f8 and a.rope), "the fused-RoPE attention has no fp8 form"
+    esz = 1 if f8 else 2
+    kvq = (lambda t: ref.quantize_kv(t)) if f8 else (lambda t: t)   # cache tensors in the chosen dtype
     nsplit, mbps = ops.decode_splits(64)
     for shp in a.shapes.split(","):
         B, ctx = (int(x) for x in shp.split("x"))
@@ -81,7 +87,7 @@ def main():
             ctxs = ctxs.sort(descending=True).values
         nb = int((ctxs.max() + 63) // 64)
         # blocks scattered over a pool 2x the live size (like a busy engine), or --pool-gb
-        blk_bytes = Hkv * 64 * D * 2 * 2
+        blk_bytes = Hkv * 64 * D * 2 * esz
         pool = max(2 * B * nb, int(a.pool_gb * 1e9 // blk_bytes))
         perm = (torch.arange(B * nb) if a.seq_blocks else torch.randperm(pool, generator=g)[: B * nb]).to(torch.int32)
         bt = perm.view(B, nb).clone()
@@ -97,7 +103,9 @@ def main():
         else:
             kc = torch.randn(pool, Hkv, 64, D, device=dev, dtype=bf)
             vc = torch.randn(pool, Hkv, 8, D, 8, device=dev, dtype=bf)
-        kvs = [(kc, vc)] + [(torch.randn_like(kc), torch.randn_like(vc)) for _ in range(a.ring - 1)]
+        kvs = [(kvq(kc), kvq(vc))] + [(kvq(torch.randn_like(kc)), kvq(torch.randn_like(vc)))
+                                     for _ in range(a.ring - 1)]
+        kc, vc = kvs[0]
         cl = ctxs.to(torch.int32).to(dev)
         q = torch.randn(B, Hq * D, device=dev, dtype=bf)
         ws = torch.empty(B * Hq * nsplit * (D + 2), device=dev, dtype=torch.float32)
@@ -137,17 +145,17 @@ def main():
         us = timeit(call)
         if not a.rope:
             ops.hip().paged_decode_attention(o, q, kc, vc, bt, cl, scale, nsplit, mbps, ws)
-        byts = int(ctxs.sum()) * Hkv * D * 2 * 2
+        byts = int(ctxs.sum()) * Hkv * D * 2 * esz
         rec = {"B": B, "ctx": ctx, "us": round(us, 2), "TBps": round(byts / us / 1e6, 2),
                "kernel": "decode_attn_kernel", "wpp": os.environ.get("LS_ATTN_WPP", "auto"),
                "pipe": os.environ.get("LS_ATTN_PIPE", "1"),
                "ragged": a.ragged, "pool_gb": a.pool_gb, "ring": a.ring, "rope": a.rope,
                "uniform_lo": a.uniform_lo, "sorted": a.sorted, "seq_blocks": a.seq_blocks,
                "shared_first": a.shared_first, "nt": os.environ.get("LS_ATTN_NT", "2"),
-               "interleave_gemm": a.interleave_gemm}
+               "interleave_gemm": a.interleave_gemm, "kv_dtype": a.kv_dtype}
         if not a.rope and (B <= 16 or (a.check_all and B * ctx <= 512 * 1024)) and a.pool_gb == 0:
             exp = ref.paged_decode_attention(q.float().cpu().reshape(B, Hq, D), kc.float().cpu(), vc.float().cpu(),
-                                             bt.cpu(), cl.cpu(), scale).reshape(B, Hq * D)
+                                             bt.cpu(), cl.cpu(), scale).reshape(B, Hq * D)   # over the dequantised cache
             rec["max_err"] = round(float((o.float().cpu() - exp).abs().max()), 4)
         print(json.dumps(rec), flush=True)
 

@@ -26,11 +26,13 @@ def bench_llm(args):
     model = LlamaModel(cfg, device="cuda")
     sync()
     print(json.dumps({"event": "model_init", "s": round(time.time() - t0, 2)}), flush=True)
-    eng = LLMEngine(model, None, max_model_len=args.max_len, max_batch=args.batch, max_prefill_tokens=args.prefill_chunk)
+    eng = LLMEngine(model, None, max_model_len=args.max_len, max_batch=args.batch, max_prefill_tokens=args.prefill_chunk,
+                    kv_cache_dtype=args.kv_dtype)
     t0 = time.time()
     eng.capture_graphs([b for b in eng.buckets if b <= args.batch])
     sync()
-    print(json.dumps({"event": "graphs", "s": round(time.time() - t0, 2), "blocks": eng.num_blocks}), flush=True)
+    print(json.dumps({"event": "graphs", "s": round(time.time() - t0, 2), "blocks": eng.num_blocks,
+                      "kv_cache_dtype": eng.kv_cache_dtype, "kv_bytes_per_block": eng.kv_bytes_per_block}), flush=True)
     sp = SamplingParams(max_tokens=args.gen, temperature=0.8, top_p=0.95, ignore_eos=True)
     prompts = [[(i * 31 + j) % 1000 + 100 for j in range(args.prompt)] for i in range(args.batch)]
     # warmup
@@ -126,6 +128,8 @@ if __name__ == "__main__":
     ap.add_argument("--gen", type=int, default=128)
     ap.add_argument("--max-len", type=int, default=4096)
     ap.add_argument("--prefill-chunk", type=int, default=16384)
+    ap.add_argument("--kv-dtype", choices=("auto", "bf16", "fp8"), default="auto",
+                    help="KV cache element type of the LLM engine (LLMEngine kv_cache_dtype)")
     ap.add_argument("--texts", type=int, default=2048)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--rows", type=int, default=1_000_000)

@@ -4,7 +4,7 @@ mean ~347), Llama-3-8B heads (32 q / 8 kv, D 128), causal; also uniform lengths.
 Reports time per call and the attention FLOP rate (causal: 2 * 2 * sum(L^2)/2 * D * Hq),
 and checks one case against the fp32 reference op.
 
-usage: python tools/prefill_attn_bench.py [--chunk 16384] [--iters 20]
+usage: python tools/prefill_attn_bench.py [--chunk 16384] [--iters 20] [--kv-dtype bf16|fp8]
 """
 import argparse
 import json
@@ -21,11 +21,13 @@ from langstream_amd import ops
 from langstream_amd.ops import reference as ref
 
 
-def build(lens, Hq=32, Hkv=8, D=128, BS=64, dev="cuda"):
+def build(lens, Hq=32, Hkv=8, D=128, BS=64, dev="cuda", kv_dtype="bf16"):
     T = sum(lens)
     nblk = sum((n + BS - 1) // BS for n in lens)
     kc = torch.randn(nblk, Hkv, BS, D, device=dev).to(torch.bfloat16)
     vc = torch.randn(nblk, Hkv, BS // 8, D, 8, device=dev).to(torch.bfloat16)
+    if kv_dtype == "fp8":   # e4m3 codes of the same values (scale 1)
+        kc, vc = ref.quantize_kv(kc), ref.quantize_kv(vc)
     maxb = max((n + BS - 1) // BS for n in lens)
     bt = torch.zeros(len(lens), maxb, dtype=torch.int32)
     b = 0
@@ -47,6 +49,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chunk", type=int, default=16384)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16", help="KV cache element type")
     a = ap.parse_args()
     rng = random.Random(0)
     Hq, D = 32, 128
@@ -63,7 +66,7 @@ def main():
     for L in (256, 512, 1024, 4096):
         mixes[f"uniform_{L}"] = [L] * (a.chunk // L)
     for name, lens in mixes.items():
-        q, kc, vc, m = build(lens)
+        q, kc, vc, m = build(lens, kv_dtype=a.kv_dtype)
         out = ops.paged_prefill_attention(q, kc, vc, m["block_tables"], m["q_start"], m["q_len"], m["ctx_len"],
                                           m["tiles"], Hq, scale)
         err = None
@@ -86,7 +89,8 @@ def main():
         us = (time.perf_counter() - t) / a.iters * 1e6
         flops = sum(2 * 2 * (n * (n + 1) / 2) * D * Hq for n in lens)
         print(json.dumps({"mix": name, "seqs": len(lens), "tokens": sum(lens), "us": round(us, 1),
-                          "TFLOPs": round(flops / us / 1e6, 1), "max_abs_err_vs_fp32": err}), flush=True)
+                          "TFLOPs": round(flops / us / 1e6, 1), "max_abs_err_vs_fp32": err,
+                          "kv_dtype": a.kv_dtype}), flush=True)
 
 
 if __name__ == "__main__":
