@@ -435,8 +435,18 @@ __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2
       bf16* op = out + ((int64_t)b * Hkv * G + head) * D + dc * CH;
 #pragma unroll
       for (int c = 0; c < CH; ++c) acc[c] *= inv;
+      if constexpr (CH >= 8) {
 #pragma unroll
-      for (int c = 0; c < CH; c += 8) st16(op + c, pack8(acc + c));
+        for (int c = 0; c < CH; c += 8) st16(op + c, pack8(acc + c));
+      } else {
+        // D = 64: a thread owns 4 dims, one 8-B store (a 16-B store would run 4 dims into
+        // the next thread's chunk, and past the row for dc = 15)
+        static_assert(CH == 4, "head dims below 64 have no decode kernel");
+        bf16x4 v;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = (bf16)acc[c];
+        *reinterpret_cast<bf16x4*>(op) = v;
+      }
     } else {
       const int64_t pi = (((int64_t)b * Hkv * G + head) * nsplit + split);
       float* po = part_o + pi * D + dc * CH;
