@@ -50,7 +50,7 @@
 // (106 us), amdgpu_waves_per_eu(3) (106.9 us).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "ops.h"
+#include "kv_write.h"
 
 namespace {
 
@@ -73,15 +73,7 @@ __device__ __forceinline__ int split_blocks(int nblk, int nsplit, int min_bps) {
 // and seeds its softmax state with the new token itself (m = s_new, l = 1, O = v_new).
 // This removes the separate rope_cache launch (~11 us per layer at B = 256 in the RAG
 // bench, profiles/rag_bench_kernel_stats_r2m.csv) from every decode step.
-struct RopeArgs {
-  const float* cos_sin;    // [max_pos, D]: cos in [0, D/2), sin in [D/2, D)
-  const int32_t* pos;      // [B]
-  int max_pos;
-  const int64_t* slots;    // [B] cache slot of the new token (-1: do not cache)
-  int64_t nslots;
-  bf16* kc;                // writable views of the caches
-  bf16* vc;
-};
+// The table row, the rotation, the slot test and the stores are those of kv_write.h.
 
 // F8: e4m3 caches (common.h "FP8 KV cache", non-ROPE form only).  K and V fragments load
 // at the same ELEMENT offsets through the same per-block descriptors, 8 bytes per lane
@@ -98,7 +90,7 @@ __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2
     bf16* __restrict__ out, const bf16* __restrict__ q, int64_t q_stride, const bf16* __restrict__ kc,
     const bf16* __restrict__ vc, const int32_t* __restrict__ block_tables, int max_blocks,
     const int32_t* __restrict__ ctx_lens, int Hkv, int G, int NB, float scale_log2, int min_bps,
-    float* __restrict__ part_o, float* __restrict__ part_ml, RopeArgs ra, float v_scale) {
+    float* __restrict__ part_o, float* __restrict__ part_ml, KvWrite kw, float v_scale) {
   static_assert(!(F8 && ROPE), "the fused-RoPE form writes bf16 K/V");
   constexpr int EB = F8 ? 1 : 2;  // bytes per cache element
   using Frag = std::conditional_t<F8, uint2, uint4>;  // 8 cache elements
@@ -122,7 +114,7 @@ __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2
   const int i16 = lane & 15, h = lane >> 4;
 
   const int ctx_all = ctx_lens[b];
-  const int p_new = ROPE ? min(max(ra.pos[b], 0), ra.max_pos - 1) : 0;
+  const float* cs = ROPE ? kv_cos_sin_row(kw, b, D) : nullptr;  // the new token's cos / sin
   // keys read from the cache: with ROPE the new token (the last one) comes from registers
   const int ctx = ROPE ? max(ctx_all - 1, 0) : ctx_all;
   const int nblk = min((ctx + BS - 1) / BS, max_blocks);
@@ -226,25 +218,25 @@ __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2
   // behind that fetch, which the first MFMA waits for anyway
   if constexpr (ROPE) {
     // cos / sin of this lane's low-half dims c = 32ks + 8h + j (ks < KS/2)
-    const float* cs = ra.cos_sin + (int64_t)p_new * D;
     float co[KS / 2][8], si[KS / 2][8];
 #pragma unroll
-    for (int ks = 0; ks < KS / 2; ++ks) {
-      const int c = 32 * ks + 8 * h;
-      *reinterpret_cast<float4*>(co[ks]) = *reinterpret_cast<const float4*>(cs + c);
-      *reinterpret_cast<float4*>(co[ks] + 4) = *reinterpret_cast<const float4*>(cs + c + 4);
-      *reinterpret_cast<float4*>(si[ks]) = *reinterpret_cast<const float4*>(cs + HALF + c);
-      *reinterpret_cast<float4*>(si[ks] + 4) = *reinterpret_cast<const float4*>(cs + HALF + c + 4);
-    }
+    for (int ks = 0; ks < KS / 2; ++ks) kv_load_cos_sin<8>(cs, D, 32 * ks + 8 * h, co[ks], si[ks]);
     auto rotate = [&](bf16x8 (&f)[KS]) {
 #pragma unroll
-      for (int ks = 0; ks < KS / 2; ++ks)
+      for (int ks = 0; ks < KS / 2; ++ks) {
+        float x1[8], x2[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const float x1 = (float)f[ks][j], x2 = (float)f[ks + KS / 2][j];
-          f[ks][j] = (bf16)(x1 * co[ks][j] - x2 * si[ks][j]);
-          f[ks + KS / 2][j] = (bf16)(x2 * co[ks][j] + x1 * si[ks][j]);
+          x1[j] = (float)f[ks][j];
+          x2[j] = (float)f[ks + KS / 2][j];
         }
+        kv_rotate<8>(co[ks], si[ks], x1, x2);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          f[ks][j] = (bf16)x1[j];
+          f[ks + KS / 2][j] = (bf16)x2[j];
+        }
+      }
     };
     rotate(qf);
     if (split == 0 && wid == 0 && ctx_all >= 1) {
@@ -273,22 +265,21 @@ __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2
       for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[dt][r] = (float)vn[dt][r];
-      const int64_t sl = ra.slots[b];
-      if (sl >= 0 && sl < ra.nslots) {
-        const int64_t blk = sl / BS, off = sl - blk * BS;
+      KvWrite w = kw;
+      w.BS = BS;  // host-checked equal; the compile-time value folds the helpers' divisions
+      KvSlot sl;
+      if (kv_slot(w, b, sl)) {
         if (i16 == 0) {
-          bf16* kd = ra.kc + ((blk * Hkv + kvh) * BS + off) * D + 8 * h;
 #pragma unroll
-          for (int ks = 0; ks < KS; ++ks) st16(kd + 32 * ks, __builtin_bit_cast(uint4, kn[ks]));
+          for (int ks = 0; ks < KS; ++ks)
+            kv_store_k<false, 8>(w, sl, kvh, D, 32 * ks + 8 * h, kn[ks]);
         }
         if (i16 < DT) {
           // V^T: lane (i16, h) stores dims 16 i16 + 4h + r (2-B stores at a 16-B stride)
-          bf16* vd = ra.vc + ((blk * Hkv + kvh) * (int64_t)D) * BS;
           bf16x4 vv = vn[0];
 #pragma unroll
           for (int dt = 1; dt < DT; ++dt) if (i16 == dt) vv = vn[dt];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) vd[vt_off(16 * i16 + 4 * h + r, (int)off, D)] = vv[r];
+          kv_store_v<false, 4>(w, sl, kvh, D, 16 * i16 + 4 * h, vv);
         }
       }
     }
@@ -504,7 +495,7 @@ int64_t decode_nsplit(int64_t B, int64_t Hkv, int64_t nsplit_max) {
 static void decode_attention_launch(at::Tensor& out, const at::Tensor& q, const at::Tensor& k_cache,
                                     const at::Tensor& v_cache, const at::Tensor& block_tables,
                                     const at::Tensor& ctx_lens, double scale, int64_t nsplit, int64_t min_bps,
-                                    const at::Tensor& workspace, const RopeArgs* ra, double k_scale = 1.0,
+                                    const at::Tensor& workspace, const KvWrite* kw, double k_scale = 1.0,
                                     double v_scale = 1.0) {
   const bool f8 = kv_is_fp8(k_cache, v_cache, "paged_decode_attention");
   TORCH_CHECK(!f8 || (k_scale > 0.0 && v_scale > 0.0), "KV cache scales must be positive");
@@ -542,7 +533,7 @@ static void decode_attention_launch(at::Tensor& out, const at::Tensor& q, const 
   // multiple of 4.  Smaller batches keep 4 waves per pair (and split long contexts).
   static const int env_wpp = env_int("LS_ATTN_WPP", 0);
   static const bool pipe = env_flag("LS_ATTN_PIPE", true);
-  const bool rope = ra != nullptr;
+  const bool rope = kw != nullptr;
   // LS_ATTN_NT (read per launch, A/B inside one process): 0 cached loads, 1 all nt, 2
   // (default) nt except each sequence's first block (the shared template-prefix block).
   // The attention kernel alone is faster all-nt (B = 256 ctx 270..550, one shared first
@@ -552,7 +543,7 @@ static void decode_attention_launch(at::Tensor& out, const at::Tensor& q, const 
   // 16.63 s vs 16.74 / 17.25 s, ab_head_attn_r5ai.log): the decode GEMMs that follow
   // lose more than the attention gains.
   const int attn_nt = env_int("LS_ATTN_NT", 2);
-  const RopeArgs rargs = rope ? *ra : RopeArgs{};
+  const KvWrite rargs = rope ? *kw : KvWrite{};
   const int wpp = env_wpp == 1 || env_wpp == 4 ? env_wpp : ((int64_t)B * Hkv >= WAVE_SLOTS && ns == 1 ? 1 : 4);
   dim3 grid(B * Hkv, ns);
   // fp8: the K scale folds into the softmax scale
@@ -596,26 +587,22 @@ void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at
                           nullptr, k_scale, v_scale);
 }
 
-// Decode-only step with RoPE and the KV-cache write fused in (see RopeArgs above).
+// Decode-only step with RoPE and the KV-cache write fused in (see above).
 // qkv: [B, (Hq + 2 Hkv) D] un-rotated projection rows (not modified); ctx_lens count the
 // new token; pos [B] int32 its position; slots [B] int64 its cache slot (-1: not cached).
 void paged_decode_attention_rope(at::Tensor out, at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin,
                                  at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, at::Tensor block_tables,
                                  at::Tensor ctx_lens, double scale, int64_t nsplit, int64_t min_bps,
                                  at::Tensor workspace) {
-  kv_require_bf16(k_cache, v_cache, "paged_decode_attention_rope");
   TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 2 && qkv.stride(1) == 1, "qkv must be [B, (Hq + 2 Hkv) D]");
+  TORCH_CHECK(k_cache.dim() == 4, "k_cache [NB, Hkv, 64, D]");
   const int64_t Hkv = k_cache.size(1), D = k_cache.size(3), B = ctx_lens.numel();
   TORCH_CHECK(qkv.size(0) == B && out.numel() % (B * D) == 0);
   const int64_t Hq = out.numel() / (B * D);
+  const KvWrite kw = make_kv_write("paged_decode_attention_rope", pos, cos_sin, slots, k_cache, v_cache, B, Hq, Hkv,
+                                   false);
   TORCH_CHECK(qkv.size(1) == (Hq + 2 * Hkv) * D, "qkv width must be (Hq + 2 Hkv) * D");
-  TORCH_CHECK(pos.scalar_type() == at::kInt && pos.is_contiguous() && pos.numel() >= B);
-  TORCH_CHECK(slots.scalar_type() == at::kLong && slots.is_contiguous() && slots.numel() >= B);
-  TORCH_CHECK(cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous() && cos_sin.dim() == 2 &&
-              cos_sin.size(1) == D && cos_sin.size(0) >= 1);
-  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous());
-  RopeArgs ra{cos_sin.data_ptr<float>(), pos.data_ptr<int32_t>(), (int)cos_sin.size(0), slots.data_ptr<int64_t>(),
-              k_cache.size(0) * BS, (bf16*)k_cache.data_ptr(), (bf16*)v_cache.data_ptr()};
+  TORCH_CHECK(pos.is_contiguous() && slots.is_contiguous());
   decode_attention_launch(out, qkv, k_cache, v_cache, block_tables, ctx_lens, scale, nsplit, min_bps, workspace,
-                          &ra);
+                          &kw);
 }

@@ -37,7 +37,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <atomic>
 #include <string>
-#include "ops.h"
+#include "kv_write.h"
 
 namespace {
 
@@ -84,15 +84,43 @@ struct DgArgs {
   const float* sumsq_in = nullptr;         // CMB_QKV / SILU_R: the producer's partials [M][npart]
   int npart = 0;
   float eps = 1e-5f, inv_h = 0.f;          // inv_h = 1 / hidden size (the mean of h^2)
-  const int32_t* pos = nullptr;            // CMB_QKV: RoPE + paged KV write
-  const float* cos_sin = nullptr;
-  int max_pos = 0;
-  const int64_t* slots = nullptr;
-  int64_t nslots = 0;
-  bf16* kc = nullptr;
-  bf16* vc = nullptr;
-  int Hq = 0, Hkv = 0, BS = 0;
+  KvWrite kw;                              // CMB_QKV: RoPE + paged KV write
 };
+
+// The last step of a qkv projection for dims 4c..4c+3 (lo) and D/2 + 4c..+3 (hi) -- the
+// RoPE pairs -- of head hd in row m, from their f32 sums: scale by rs, rotate q and k
+// heads in f32, store the bf16 row, and for k / v heads write the paged cache (K rows, V
+// transposed: kv_write.h), the cache values being the bf16 values of the row.
+template <int D, bool F8>
+__device__ __forceinline__ void qkv_finish(const KvWrite& kw, f32x4 lo, f32x4 hi, float rs, int m, int hd, int c,
+                                           bf16* __restrict__ out, int64_t ldo) {
+  constexpr int HALF = D / 2;
+  float a[4], b[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    a[j] = lo[j] * rs;
+    b[j] = hi[j] * rs;
+  }
+  if (hd < kw.Hq + kw.Hkv) {
+    float co[4], si[4];
+    kv_load_cos_sin<4>(kv_cos_sin_row(kw, m, D), D, 4 * c, co, si);
+    kv_rotate<4>(co, si, a, b);
+  }
+  const bf16x4 va = {(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3]};
+  const bf16x4 vb = {(bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
+  bf16* orow = out + (int64_t)m * ldo + (int64_t)hd * D + 4 * c;
+  *reinterpret_cast<bf16x4*>(orow) = va;
+  *reinterpret_cast<bf16x4*>(orow + HALF) = vb;
+  KvSlot s;
+  if (hd < kw.Hq || !kv_slot(kw, m, s)) return;
+  if (hd < kw.Hq + kw.Hkv) {
+    kv_store_k<F8, 4>(kw, s, hd - kw.Hq, D, 4 * c, va);
+    kv_store_k<F8, 4>(kw, s, hd - kw.Hq, D, HALF + 4 * c, vb);
+  } else {
+    kv_store_v<F8, 4>(kw, s, hd - kw.Hq - kw.Hkv, D, 4 * c, va);
+    kv_store_v<F8, 4>(kw, s, hd - kw.Hq - kw.Hkv, D, HALF + 4 * c, vb);
+  }
+}
 
 // 1 / rms of one row from its npart partial sums of squares.  The partials were written by
 // the previous launch from every XCD, so each load is a MALL / cross-XCD round trip: the
@@ -550,46 +578,7 @@ __global__ void __launch_bounds__(LD ? 768 : 512) dgemm_kernel(const bf16* __res
           lo += *reinterpret_cast<const f32x4*>(part + s * MN + e0);
           hi += *reinterpret_cast<const f32x4*>(part + s * MN + e0 + HALF);
         }
-        const float rs = rrow[i];
-        float a[4], b[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          a[j] = lo[j] * rs;
-          b[j] = hi[j] * rs;
-        }
-        if (hd < ga.Hq + ga.Hkv) {
-          const int pp = min(max(ga.pos[m], 0), ga.max_pos - 1);
-          const float4 co = *reinterpret_cast<const float4*>(ga.cos_sin + (int64_t)pp * D + 4 * c4);
-          const float4 si = *reinterpret_cast<const float4*>(ga.cos_sin + (int64_t)pp * D + HALF + 4 * c4);
-          const float cv[4] = {co.x, co.y, co.z, co.w}, sv[4] = {si.x, si.y, si.z, si.w};
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float x1 = a[j], x2 = b[j];
-            a[j] = x1 * cv[j] - x2 * sv[j];
-            b[j] = x2 * cv[j] + x1 * sv[j];
-          }
-        }
-        const bf16x4 va = {(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3]};
-        const bf16x4 vb = {(bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
-        bf16* orow = out + (int64_t)m * ldo + (int64_t)hd * D + 4 * c4;
-        *reinterpret_cast<bf16x4*>(orow) = va;
-        *reinterpret_cast<bf16x4*>(orow + HALF) = vb;
-        if (hd < ga.Hq) continue;
-        const int64_t sl = ga.slots[m];
-        if (sl < 0 || sl >= ga.nslots) continue;
-        const int64_t blk = sl / ga.BS, off = sl - blk * ga.BS;
-        if (hd < ga.Hq + ga.Hkv) {
-          bf16* kd = ga.kc + ((blk * ga.Hkv + (hd - ga.Hq)) * ga.BS + off) * D + 4 * c4;
-          *reinterpret_cast<bf16x4*>(kd) = va;
-          *reinterpret_cast<bf16x4*>(kd + HALF) = vb;
-        } else {
-          bf16* vd = ga.vc + ((blk * ga.Hkv + (hd - ga.Hq - ga.Hkv)) * (int64_t)D) * ga.BS;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            vd[vt_off(4 * c4 + j, (int)off, D)] = va[j];
-            vd[vt_off(HALF + 4 * c4 + j, (int)off, D)] = vb[j];
-          }
-        }
+        qkv_finish<D, false>(ga.kw, lo, hi, rrow[i], m, hd, c4, out, ldo);
       }
     }
   }
@@ -804,22 +793,17 @@ void decode_gemm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspac
 // ---------------------------------------------------------------------------------
 // qkv projection of a decode-only step: the split-K reduction fused with RoPE and the
 // paged KV-cache write.  One thread per (row m, head hd, 4-dim group c < D/8): it sums
-// the S partial slabs of dims 4c..4c+3 and D/2+4c..+3 (the RoPE pairs), rotates q and k
-// heads in f32 (cos / sin of position pos[m]), stores the bf16 row, and for k / v heads
-// writes the paged cache (K rows, V transposed: see rope.hip).  This replaces the plain
+// the S partial slabs of dims 4c..4c+3 and D/2+4c..+3 (the RoPE pairs) and hands them to
+// qkv_finish.  This replaces the plain
 // split-K reduce + the separate RoPE/cache pass (the attention then runs its un-fused
 // form: the fused-RoPE attention measured 91.6 vs 80.4 us at B = 256, ctx 410,
 // profiles/decode_attn_rope_isolated_r3.log).
-// F8: e4m3 caches (common.h "FP8 KV cache"), codes from the bf16-rounded values of the row;
-// K as two 4-byte stores, V as 1-byte stores at an 8-byte stride.
+// F8: e4m3 caches; K as two 4-byte stores, V as 1-byte stores at an 8-byte stride.
 template <int D, bool F8>
-__global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(
-    const float* __restrict__ part, int S, int M, int N, bf16* __restrict__ out, int64_t ldo,
-    const int32_t* __restrict__ pos, const float* __restrict__ cos_sin, int max_pos,
-    const int64_t* __restrict__ slots, int64_t nslots, bf16* __restrict__ kc, bf16* __restrict__ vc, int Hq, int Hkv,
-    int BS, float inv_k, float inv_v) {
+__global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(const float* __restrict__ part, int S, int M, int N,
+                                                                 bf16* __restrict__ out, int64_t ldo, KvWrite kw) {
   constexpr int HALF = D / 2, G4 = HALF / 4;
-  const int H = Hq + 2 * Hkv;
+  const int H = kw.Hq + 2 * kw.Hkv;
   const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (tid >= (int64_t)M * H * G4) return;
   const int c = (int)(tid % G4);
@@ -849,57 +833,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(
     a[0] += x.x; a[1] += x.y; a[2] += x.z; a[3] += x.w;
     b[0] += y.x; b[1] += y.y; b[2] += y.z; b[3] += y.w;
   }
-  if (hd < Hq + Hkv) {
-    const int p = min(max(pos[m], 0), max_pos - 1);
-    const float4 co = *reinterpret_cast<const float4*>(cos_sin + (int64_t)p * D + 4 * c);
-    const float4 si = *reinterpret_cast<const float4*>(cos_sin + (int64_t)p * D + HALF + 4 * c);
-    const float cv[4] = {co.x, co.y, co.z, co.w}, sv[4] = {si.x, si.y, si.z, si.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float x1 = a[j], x2 = b[j];
-      a[j] = x1 * cv[j] - x2 * sv[j];
-      b[j] = x2 * cv[j] + x1 * sv[j];
-    }
-  }
-  const bf16x4 va = {(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3]};
-  const bf16x4 vb = {(bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
-  bf16* orow = out + (int64_t)m * ldo + (int64_t)hd * D + 4 * c;
-  *reinterpret_cast<bf16x4*>(orow) = va;
-  *reinterpret_cast<bf16x4*>(orow + HALF) = vb;
-  if (hd < Hq) return;
-  const int64_t sl = slots[m];
-  if (sl < 0 || sl >= nslots) return;
-  const int64_t blk = sl / BS, off = sl - blk * BS;
-  if (hd < Hq + Hkv) {
-    const int64_t ko = ((blk * Hkv + (hd - Hq)) * BS + off) * D + 4 * c;
-    if constexpr (F8) {
-      fp8_t* kd = reinterpret_cast<fp8_t*>(kc) + ko;
-      *reinterpret_cast<uint32_t*>(kd) = fp8_pack4((float)va[0], (float)va[1], (float)va[2], (float)va[3], inv_k);
-      *reinterpret_cast<uint32_t*>(kd + HALF) =
-          fp8_pack4((float)vb[0], (float)vb[1], (float)vb[2], (float)vb[3], inv_k);
-    } else {
-      bf16* kd = kc + ko;
-      *reinterpret_cast<bf16x4*>(kd) = va;
-      *reinterpret_cast<bf16x4*>(kd + HALF) = vb;
-    }
-  } else {
-    const int64_t vo = ((blk * Hkv + (hd - Hq - Hkv)) * (int64_t)D) * BS;
-    if constexpr (F8) {
-      fp8_t* vd = reinterpret_cast<fp8_t*>(vc) + vo;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        vd[vt_off(4 * c + j, (int)off, D)] = fp8_from_bf16(va[j], inv_v);
-        vd[vt_off(HALF + 4 * c + j, (int)off, D)] = fp8_from_bf16(vb[j], inv_v);
-      }
-    } else {
-      bf16* vd = vc + vo;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        vd[vt_off(4 * c + j, (int)off, D)] = va[j];
-        vd[vt_off(HALF + 4 * c + j, (int)off, D)] = vb[j];
-      }
-    }
-  }
+  qkv_finish<D, F8>(kw, f32x4{a[0], a[1], a[2], a[3]}, f32x4{b[0], b[1], b[2], b[3]}, 1.f, m, hd, c, out, ldo);
 }
 
 // qkv[M, (Hq + 2 Hkv) D] = RoPE(x . w^T) for q and k heads, with the step's K / V rows
@@ -908,16 +842,13 @@ void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor
                           at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, int64_t Hq,
                           int64_t Hkv, double k_scale, double v_scale) {
   check_xw(x, w);
-  const bool f8 = kv_is_fp8(k_cache, v_cache, "decode_gemm_qkv_rope");
   const int M = (int)x.size(0), K = (int)x.size(1), N = (int)w.size(0);
-  const int D = (int)k_cache.size(3), BSZ = (int)k_cache.size(2);
+  bool f8;
+  const KvWrite kw = make_kv_write("decode_gemm_qkv_rope", pos, cos_sin, slots, k_cache, v_cache, M, Hq, Hkv, true,
+                                   k_scale, v_scale, &f8);
+  const int D = (int)k_cache.size(3);
   TORCH_CHECK(N == (Hq + 2 * Hkv) * D && N % 128 == 0, "decode_gemm_qkv_rope: qkv width");
   TORCH_CHECK(qkv.scalar_type() == at::kBFloat16 && qkv.size(0) == M && qkv.size(1) == N && qkv.stride(1) == 1);
-  TORCH_CHECK(pos.scalar_type() == at::kInt && pos.numel() >= M && slots.scalar_type() == at::kLong &&
-              slots.numel() >= M && cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous() &&
-              cos_sin.size(1) == D, "decode_gemm_qkv_rope: pos / slots / cos_sin");
-  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous() && v_cache.dim() == 5 && v_cache.size(2) == BSZ / 8 &&
-              v_cache.size(3) == D && v_cache.size(4) == 8, "decode_gemm_qkv_rope: v_cache [NB, Hkv, BS/8, D, 8]");
   const int bn = pick_bn(N), tiles = N / bn;
   // at most 4 K slices: the fused reduction reads every slab once more (qkv at M = 256:
   // 27.5 us with 4 slices vs 28.1 with the 5 pick_split chooses, profiles/dgemm_bench_r3b.log)
@@ -936,12 +867,9 @@ void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor
   else
     dgemm_launch<128, EPI_PARTIAL>(S, tiles, st, x, w, M, N, K, nullptr, 0, part, 0, nullptr, nullptr, nullptr);
   const int64_t threads = (int64_t)M * (Hq + 2 * Hkv) * (D / 8);
-  const float inv_k = kv_inv_scale(k_scale), inv_v = kv_inv_scale(v_scale);
-#define LAUNCH_RR(FF)                                                                                              \
-  splitk_reduce_rope_kernel<128, FF><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(                          \
-      part, S, M, N, (bf16*)qkv.data_ptr(), qkv.stride(0), pos.data_ptr<int32_t>(), cos_sin.data_ptr<float>(),    \
-      (int)cos_sin.size(0), slots.data_ptr<int64_t>(), k_cache.size(0) * BSZ, (bf16*)k_cache.data_ptr(),          \
-      (bf16*)v_cache.data_ptr(), (int)Hq, (int)Hkv, BSZ, inv_k, inv_v)
+#define LAUNCH_RR(FF)                                                                     \
+  splitk_reduce_rope_kernel<128, FF><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>( \
+      part, S, M, N, (bf16*)qkv.data_ptr(), qkv.stride(0), kw)
   if (f8) LAUNCH_RR(true); else LAUNCH_RR(false);
 #undef LAUNCH_RR
 }
@@ -1104,20 +1032,15 @@ void decode_gemm_res(at::Tensor y_out, at::Tensor x, at::Tensor w, at::Tensor wo
 void decode_gemm_qkv_cmb(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor counters,
                          at::Tensor sumsq_in, double eps, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots,
                          at::Tensor k_cache, at::Tensor v_cache, int64_t Hq, int64_t Hkv, at::Tensor err) {
-  kv_require_bf16(k_cache, v_cache, "decode_gemm_qkv_cmb");
   const int M = (int)x.size(0), K = (int)x.size(1), N = (int)w.size(0);
+  const KvWrite kw = make_kv_write("decode_gemm_qkv_cmb", pos, cos_sin, slots, k_cache, v_cache, M, Hq, Hkv, false);
   const int S = (int)decode_gemm_cmb_splits(N, K);
   check_cmb_common(x, w, workspace, counters, err, S);
-  const int D = (int)k_cache.size(3), BSZ = (int)k_cache.size(2);
+  const int D = (int)k_cache.size(3);
   TORCH_CHECK(D == 128 && N == (Hq + 2 * Hkv) * D, "decode_gemm_qkv_cmb: head dim 128, qkv width");
   TORCH_CHECK(qkv.scalar_type() == at::kBFloat16 && qkv.size(0) == M && qkv.size(1) == N && qkv.stride(1) == 1);
   TORCH_CHECK(sumsq_in.scalar_type() == at::kFloat && sumsq_in.is_contiguous() && sumsq_in.dim() == 2 &&
               sumsq_in.size(0) >= M, "decode_gemm_qkv_cmb: sumsq_in f32 [M, npart]");
-  TORCH_CHECK(pos.scalar_type() == at::kInt && pos.numel() >= M && slots.scalar_type() == at::kLong &&
-              slots.numel() >= M && cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous() &&
-              cos_sin.size(1) == D, "decode_gemm_qkv_cmb: pos / slots / cos_sin");
-  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous() && v_cache.dim() == 5 && v_cache.size(2) == BSZ / 8 &&
-              v_cache.size(3) == D && v_cache.size(4) == 8, "decode_gemm_qkv_cmb: v_cache [NB, Hkv, BS/8, D, 8]");
   DgArgs ga;
   ga.counters = reinterpret_cast<unsigned long long*>(counters.data_ptr<int64_t>());
   ga.err = err.data_ptr<int>();
@@ -1125,16 +1048,7 @@ void decode_gemm_qkv_cmb(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor 
   ga.npart = (int)sumsq_in.size(1);
   ga.eps = (float)eps;
   ga.inv_h = 1.f / (float)K;
-  ga.pos = pos.data_ptr<int32_t>();
-  ga.cos_sin = cos_sin.data_ptr<float>();
-  ga.max_pos = (int)cos_sin.size(0);
-  ga.slots = slots.data_ptr<int64_t>();
-  ga.nslots = k_cache.size(0) * BSZ;
-  ga.kc = (bf16*)k_cache.data_ptr();
-  ga.vc = (bf16*)v_cache.data_ptr();
-  ga.Hq = (int)Hq;
-  ga.Hkv = (int)Hkv;
-  ga.BS = BSZ;
+  ga.kw = kw;
   dgemm_launch<128, EPI_CMB_QKV>(S, N / 128, at::hip::getCurrentHIPStream(), x, w, M, N, K,
                                  (bf16*)qkv.data_ptr(), qkv.stride(0), workspace.data_ptr<float>(), 0, nullptr,
                                  nullptr, nullptr, ga);

@@ -21,7 +21,7 @@
 // writes silu(gate) * up as [T, F] (replacing the gate_up GEMM + silu_and_mul pair).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "ops.h"
+#include "kv_write.h"
 
 namespace {
 
@@ -56,15 +56,7 @@ struct ProNorm {
 // RB/2 rotary pairs (d, d + D/2) of one head, so the epilogue applies RoPE to q and k heads
 // and writes k to the paged K cache [NB, Hkv, BS, D] and v transposed to the V cache
 // [NB, Hkv, BS/8, D, 8] -- the rope_cache kernel of rope.hip, fused (same bf16 rounding).
-struct QkvEpi {
-  const int32_t* pos;
-  const float* cos_sin;  // [max_pos, D]: cols [0, D/2) cos, [D/2, D) sin
-  const int64_t* slots;  // [T] cache slot, -1 = not cached
-  bf16* kc;
-  bf16* vc;
-  int64_t nslots;
-  int Hq, Hkv, BS, D, max_pos, apply_rope;
-};
+// The kernel takes the KvWrite of kv_write.h, the head dim qD and the apply_rope flag.
 
 // 8-element bf16 dot on v_dot2c_f32_bf16.  The pairs are taken with shufflevector on the
 // whole 16-B value: bit-casting extracted u32 elements (a.y, a[1], ...) is miscompiled by
@@ -87,18 +79,18 @@ __device__ __forceinline__ float dot8(u32x4 a, u32x4 b, float acc) {
 template <int TR, int KCH, int RB, int EPI, bool PRO>
 __global__ void __launch_bounds__(256) gemv_kernel(const bf16* __restrict__ x, int T, const bf16* __restrict__ W,
                                                    int N, int K, bf16* __restrict__ out, int ldo, AddNorm an,
-                                                   ProNorm pro, QkvEpi qe) {
+                                                   ProNorm pro, KvWrite kw, int qD, int apply_rope) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int nchunk = K >> 9;  // K % 512 == 0 (host-checked)
   constexpr int HALF = RB / 2;
   const int F = N >> 1;
   const int base = blockIdx.x * (EPI == EPI_SILU ? HALF : RB);
   // EPI_QKV: head and first rotary index of this block's HALF pairs
-  const int qk_bph = EPI == EPI_QKV ? (qe.D / 2) / HALF : 1;
+  const int qk_bph = EPI == EPI_QKV ? (qD / 2) / HALF : 1;
   const int qk_head = blockIdx.x / qk_bph, qk_j0 = (blockIdx.x % qk_bph) * HALF;
   auto w_row = [&](int r) -> int {
     if constexpr (EPI == EPI_SILU) return r < HALF ? base + r : F + base + r - HALF;
-    else if constexpr (EPI == EPI_QKV) return qk_head * qe.D + (r < HALF ? qk_j0 + r : qe.D / 2 + qk_j0 + r - HALF);
+    else if constexpr (EPI == EPI_QKV) return qk_head * qD + (r < HALF ? qk_j0 + r : qD / 2 + qk_j0 + r - HALF);
     else return base + r;
   };
   u32x4 wr[RB][KCH];
@@ -274,35 +266,28 @@ __global__ void __launch_bounds__(256) gemv_kernel(const bf16* __restrict__ x, i
     if (t < HALF * TR) {
       const int u = t / TR, m = t % TR;
       if (m < T) {
-        const int hd = qe.D / 2;
         const int i1 = u * TR + m, i2 = (u + HALF) * TR + m;
         // the unfused path rounds the projection to bf16 before rotating
         float a = (float)(bf16)(red[0][i1] + red[1][i1] + red[2][i1] + red[3][i1]);
         float b = (float)(bf16)(red[0][i2] + red[1][i2] + red[2][i2] + red[3][i2]);
-        const int d1 = qk_j0 + u, d2 = hd + qk_j0 + u;
-        const bool rot = qe.apply_rope && qk_head < qe.Hq + qe.Hkv;
-        if (rot) {
-          const int p = min(max(qe.pos[m], 0), qe.max_pos - 1);
-          const float co = qe.cos_sin[(int64_t)p * qe.D + d1], si = qe.cos_sin[(int64_t)p * qe.D + hd + d1];
-          const float x1 = a, x2 = b;
-          a = x1 * co - x2 * si;
-          b = x2 * co + x1 * si;
+        const int d1 = qk_j0 + u, d2 = qD / 2 + d1;
+        if (apply_rope && qk_head < kw.Hq + kw.Hkv) {
+          float co, si;
+          kv_load_cos_sin<1>(kv_cos_sin_row(kw, m, qD), qD, d1, &co, &si);
+          kv_rotate<1>(&co, &si, &a, &b);
         }
         const bf16 ab = (bf16)a, bb = (bf16)b;
-        bf16* orow = out + (int64_t)m * ldo + qk_head * qe.D;
+        bf16* orow = out + (int64_t)m * ldo + qk_head * qD;
         orow[d1] = ab;
         orow[d2] = bb;
-        const int64_t s = qe.slots[m];
-        if (qk_head >= qe.Hq && s >= 0 && s < qe.nslots) {
-          const int64_t blk = s / qe.BS, off = s - blk * qe.BS;
-          if (qk_head < qe.Hq + qe.Hkv) {
-            bf16* kd = qe.kc + ((blk * qe.Hkv + (qk_head - qe.Hq)) * qe.BS + off) * qe.D;
-            kd[d1] = ab;
-            kd[d2] = bb;
+        KvSlot s;
+        if (qk_head >= kw.Hq && kv_slot(kw, m, s)) {
+          if (qk_head < kw.Hq + kw.Hkv) {
+            kv_store_k<false, 1>(kw, s, qk_head - kw.Hq, qD, d1, ab);
+            kv_store_k<false, 1>(kw, s, qk_head - kw.Hq, qD, d2, bb);
           } else {
-            bf16* vd = qe.vc + (blk * qe.Hkv + (qk_head - qe.Hq - qe.Hkv)) * (int64_t)qe.D * qe.BS;
-            vd[vt_off(d1, (int)off, qe.D)] = ab;
-            vd[vt_off(d2, (int)off, qe.D)] = bb;
+            kv_store_v<false, 1>(kw, s, qk_head - kw.Hq - kw.Hkv, qD, d1, ab);
+            kv_store_v<false, 1>(kw, s, qk_head - kw.Hq - kw.Hkv, qD, d2, bb);
           }
         }
       }
@@ -398,7 +383,8 @@ __global__ void __launch_bounds__(256) gemv_kernel(const bf16* __restrict__ x, i
 struct Extra {
   AddNorm an{};
   ProNorm pro{};
-  QkvEpi qe{};
+  KvWrite kw{};  // EPI_QKV, with the head dim and the rotate flag
+  int qD = 0, apply_rope = 0;
 };
 
 template <int TR, int KCH, int EPI, bool PRO>
@@ -413,10 +399,10 @@ void launch_rb(const at::Tensor& x, const at::Tensor& w, at::Tensor& out, int T,
   const int rows_per_block = EPI == EPI_SILU ? RB / 2 : RB;
   const int nrows = EPI == EPI_SILU ? N / 2 : N;
   TORCH_CHECK(nrows % rows_per_block == 0, "gemv: output rows must be a multiple of ", rows_per_block);
-  if (EPI == EPI_QKV) TORCH_CHECK((ex.qe.D / 2) % (RB / 2) == 0, "gemv_qkv: head_dim / 2 must divide by ", RB / 2);
+  if (EPI == EPI_QKV) TORCH_CHECK((ex.qD / 2) % (RB / 2) == 0, "gemv_qkv: head_dim / 2 must divide by ", RB / 2);
   gemv_kernel<TR, KCH, RB, EPI, PRO><<<nrows / rows_per_block, 256, 0, st>>>(
       (const bf16*)x.data_ptr(), T, (const bf16*)w.data_ptr(), N, K, (bf16*)out.data_ptr(), (int)out.stride(0), ex.an,
-      ex.pro, ex.qe);
+      ex.pro, ex.kw, ex.qD, ex.apply_rope);
 }
 
 template <int TR, int EPI, bool PRO>
@@ -466,22 +452,6 @@ ProNorm make_pro(const at::Tensor& o, const at::Tensor& res, const at::Tensor& r
   TORCH_CHECK(res_out.data_ptr() != res.data_ptr(), "gemv_norm: res_out must not alias res");
   return ProNorm{(const bf16*)o.data_ptr(), (const bf16*)res.data_ptr(), (bf16*)res_out.data_ptr(),
                  (const bf16*)norm_w.data_ptr(), (float)eps};
-}
-
-QkvEpi make_qkv(const at::Tensor& out, const at::Tensor& pos, const at::Tensor& cos_sin, const at::Tensor& slots,
-                const at::Tensor& kc, const at::Tensor& vc, int64_t Hq, int64_t Hkv, bool apply_rope) {
-  TORCH_CHECK(pos.scalar_type() == at::kInt && slots.scalar_type() == at::kLong && cos_sin.scalar_type() == at::kFloat &&
-                  cos_sin.is_contiguous(), "gemv_qkv: pos int32, slots int64, cos_sin f32");
-  kv_require_bf16(kc, vc, "gemv_qkv");
-  TORCH_CHECK(kc.dim() == 4 && vc.dim() == 5, "gemv_qkv: paged caches [NB, Hkv, BS, D] / [NB, Hkv, BS/8, D, 8] bf16");
-  const int D = kc.size(3), BS = kc.size(2);
-  TORCH_CHECK(kc.size(1) == Hkv && vc.size(1) == Hkv && vc.size(2) == BS / 8 && vc.size(3) == D && vc.size(4) == 8 &&
-                  cos_sin.size(1) == D, "gemv_qkv: cache / rope table shapes");
-  TORCH_CHECK(out.size(1) == (Hq + 2 * Hkv) * D && pos.numel() == out.size(0) && slots.numel() == out.size(0),
-              "gemv_qkv: qkv / pos / slots shapes");
-  return QkvEpi{pos.data_ptr<int32_t>(), cos_sin.data_ptr<float>(), slots.data_ptr<int64_t>(), (bf16*)kc.data_ptr(),
-                (bf16*)vc.data_ptr(), kc.size(0) * (int64_t)BS, (int)Hq, (int)Hkv, BS, D, (int)cos_sin.size(0),
-                apply_rope ? 1 : 0};
 }
 
 template <int EPI>
@@ -534,7 +504,12 @@ void gemv_qkv(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor pos, at::Te
               c10::optional<at::Tensor> o, c10::optional<at::Tensor> res, c10::optional<at::Tensor> res_out,
               c10::optional<at::Tensor> norm_w, double eps) {
   Extra ex;
-  ex.qe = make_qkv(out, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope);
+  TORCH_CHECK(out.dim() == 2, "gemv_qkv: qkv [T, (Hq + 2 Hkv) D]");
+  ex.kw = make_kv_write("gemv_qkv", pos, cos_sin, slots, k_cache, v_cache, out.size(0), Hq, Hkv, false);
+  ex.qD = (int)k_cache.size(3);
+  ex.apply_rope = apply_rope ? 1 : 0;
+  TORCH_CHECK(out.size(1) == (Hq + 2 * Hkv) * ex.qD && pos.numel() == out.size(0) && slots.numel() == out.size(0),
+              "gemv_qkv: qkv / pos / slots shapes");
   if (o.has_value()) {
     TORCH_CHECK(res.has_value() && res_out.has_value() && norm_w.has_value(), "gemv_qkv: prologue operands");
     ex.pro = make_pro(*o, *res, *res_out, *norm_w, eps);

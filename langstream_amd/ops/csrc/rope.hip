@@ -9,6 +9,7 @@
 // v_cache  : [NB, Hkv, BS/8, D, 8]   (TRANSPOSED in 8-key groups: 8 keys of one dim are
 //            16 contiguous bytes, so attention reads V^T MFMA fragments with one 16-B load
 //            per lane; a token's V lands at a 16-B stride -- common.h vt_off)
+// The rotation, the slot test and the cache stores are those of kv_write.h.
 //
 // Grid: x = tiles of TOK tokens, y = head groups.  y < nq: rotate HG query heads;
 // nq <= y < nq+nk: rotate HG key heads and store them to the K cache; the last Hkv
@@ -18,7 +19,7 @@
 // (T/16) x (Hq/8 + Hkv/8 + Hkv) workgroups instead of one.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "ops.h"
+#include "kv_write.h"
 
 namespace {
 
@@ -30,18 +31,14 @@ constexpr int TOK_SMALL = 2;
 constexpr int64_t SMALL_T = 2048;
 constexpr int HG = 8;    // heads per rotate workgroup
 
-// F8: e4m3 caches (common.h "FP8 KV cache"): the same element offsets at 1 byte each; K as
-// one 8-byte store per 8 rotated values, V as 1-byte stores at an 8-byte stride.  The codes
-// come from the bf16-rounded values the qkv row gets.
+// F8: e4m3 caches (kv_write.h): K as one 8-byte store per 8 rotated values, V as 1-byte
+// stores at an 8-byte stride.
 template <int D, int TOK, bool F8>
-__global__ void __launch_bounds__(256) rope_cache_kernel(bf16* __restrict__ qkv, const int32_t* __restrict__ pos,
-                                                         const float* __restrict__ cos_sin,
-                                                         const int64_t* __restrict__ slots, bf16* __restrict__ kc,
-                                                         bf16* __restrict__ vc, int64_t T, int Hq, int Hkv, int BS,
-                                                         int max_pos, int apply_rope, int64_t nslots, float inv_k,
-                                                         float inv_v) {
+__global__ void __launch_bounds__(256) rope_cache_kernel(bf16* __restrict__ qkv, KvWrite kw, int64_t T,
+                                                         int apply_rope) {
   constexpr int HALF = D / 2;
   constexpr int VPH = HALF / 8;  // 16-B vectors per half head
+  const int Hq = kw.Hq, Hkv = kw.Hkv;
   const int64_t t0 = (int64_t)blockIdx.x * TOK;
   const int ntok = (int)min((int64_t)TOK, T - t0);
   const int row_elems = (Hq + 2 * Hkv) * D;
@@ -64,38 +61,17 @@ __global__ void __launch_bounds__(256) rope_cache_kernel(bf16* __restrict__ qkv,
       unpack8(ld16(base + c * 8), a);
       unpack8(ld16(base + HALF + c * 8), b);
       if (apply_rope) {
-        const int p = min(max(pos[t], 0), max_pos - 1);
-        const float* cs = cos_sin + (int64_t)p * D;
         float co[8], si[8];
-        *reinterpret_cast<float4*>(co) = *reinterpret_cast<const float4*>(cs + c * 8);
-        *reinterpret_cast<float4*>(co + 4) = *reinterpret_cast<const float4*>(cs + c * 8 + 4);
-        *reinterpret_cast<float4*>(si) = *reinterpret_cast<const float4*>(cs + HALF + c * 8);
-        *reinterpret_cast<float4*>(si + 4) = *reinterpret_cast<const float4*>(cs + HALF + c * 8 + 4);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float x1 = a[j], x2 = b[j];
-          a[j] = x1 * co[j] - x2 * si[j];
-          b[j] = x2 * co[j] + x1 * si[j];
-        }
+        kv_load_cos_sin<8>(kv_cos_sin_row(kw, t, D), D, c * 8, co, si);
+        kv_rotate<8>(co, si, a, b);
       }
       const uint4 pa = pack8(a), pb = pack8(b);
       st16(base + c * 8, pa);
       st16(base + HALF + c * 8, pb);
-      if (is_k) {
-        const int64_t s = slots[t];
-        if (s >= 0 && s < nslots) {
-          const int64_t blk = s / BS, off = s - blk * BS;
-          const int64_t ko = ((blk * Hkv + (h - Hq)) * BS + off) * D;
-          if constexpr (F8) {
-            fp8_t* kd = reinterpret_cast<fp8_t*>(kc) + ko;
-            *reinterpret_cast<uint2*>(kd + c * 8) = fp8_pack8(__builtin_bit_cast(bf16x8, pa), inv_k);
-            *reinterpret_cast<uint2*>(kd + HALF + c * 8) = fp8_pack8(__builtin_bit_cast(bf16x8, pb), inv_k);
-          } else {
-            bf16* kd = kc + ko;
-            st16(kd + c * 8, pa);
-            st16(kd + HALF + c * 8, pb);
-          }
-        }
+      KvSlot s;
+      if (is_k && kv_slot(kw, t, s)) {
+        kv_store_k<F8, 8>(kw, s, h - Hq, D, c * 8, __builtin_bit_cast(bf16x8, pa));
+        kv_store_k<F8, 8>(kw, s, h - Hq, D, HALF + c * 8, __builtin_bit_cast(bf16x8, pb));
       }
     }
     return;
@@ -106,18 +82,10 @@ __global__ void __launch_bounds__(256) rope_cache_kernel(bf16* __restrict__ qkv,
   const int dr = threadIdx.x / TOK;  // 0..256/TOK-1
   if (tl >= ntok) return;
   const int64_t t = t0 + tl;
-  const int64_t s = slots[t];
-  if (s < 0 || s >= nslots) return;
-  const int64_t blk = s / BS, off = s - blk * BS;
+  KvSlot s;
+  if (!kv_slot(kw, t, s)) return;
   const bf16* src = qkv + t * row_elems + (Hq + Hkv + hv) * D;
-  const int64_t vo = ((blk * Hkv + hv) * (int64_t)D) * BS;
-  if constexpr (F8) {
-    fp8_t* vd = reinterpret_cast<fp8_t*>(vc) + vo;
-    for (int d = dr; d < D; d += 256 / TOK) vd[vt_off(d, (int)off, D)] = fp8_from_bf16(src[d], inv_v);
-  } else {
-    bf16* vd = vc + vo;
-    for (int d = dr; d < D; d += 256 / TOK) vd[vt_off(d, (int)off, D)] = src[d];
-  }
+  for (int d = dr; d < D; d += 256 / TOK) kv_store_v<F8, 1>(kw, s, hv, D, d, src[d]);
 }
 
 }  // namespace
@@ -126,30 +94,22 @@ void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tens
                     at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope, double k_scale,
                     double v_scale) {
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.is_contiguous());
-  TORCH_CHECK(pos.scalar_type() == at::kInt && slots.scalar_type() == at::kLong);
-  TORCH_CHECK(cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous());
-  const bool f8 = kv_is_fp8(k_cache, v_cache, "rope_and_cache");
-  TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 5, "k_cache [NB, Hkv, BS, D], v_cache [NB, Hkv, BS/8, D, 8]");
+  TORCH_CHECK(k_cache.dim() == 4, "k_cache [NB, Hkv, BS, D], v_cache [NB, Hkv, BS/8, D, 8]");
   const int D = k_cache.size(3);
-  const int BS = k_cache.size(2);
-  TORCH_CHECK(k_cache.size(1) == Hkv && v_cache.size(1) == Hkv && v_cache.size(2) == BS / 8 && v_cache.size(3) == D &&
-              v_cache.size(4) == 8);
   TORCH_CHECK(qkv.size(-1) == (Hq + 2 * Hkv) * D);
   const int64_t T = qkv.numel() / qkv.size(-1);
+  bool f8;
+  const KvWrite kw = make_kv_write("rope_and_cache", pos, cos_sin, slots, k_cache, v_cache, T, Hq, Hkv, true,
+                                   k_scale, v_scale, &f8);
   TORCH_CHECK(pos.numel() == T && slots.numel() == T);
-  TORCH_CHECK(cos_sin.size(1) == D);
   if (T == 0) return;
   auto stream = at::hip::getCurrentHIPStream();
   const int nq = (int)((Hq + HG - 1) / HG), nk = (int)((Hkv + HG - 1) / HG);
   const bool small = T <= SMALL_T;
   const int tok = small ? TOK_SMALL : TOK_LARGE;
   dim3 grid((unsigned)((T + tok - 1) / tok), nq + nk + (int)Hkv);
-  const float inv_k = kv_inv_scale(k_scale), inv_v = kv_inv_scale(v_scale);
-#define LAUNCH_F(DD, TT, FF)                                                                                \
-  rope_cache_kernel<DD, TT, FF><<<grid, 256, 0, stream>>>(                                                  \
-      (bf16*)qkv.data_ptr(), pos.data_ptr<int32_t>(), cos_sin.data_ptr<float>(), slots.data_ptr<int64_t>(), \
-      (bf16*)k_cache.data_ptr(), (bf16*)v_cache.data_ptr(), T, (int)Hq, (int)Hkv, BS, (int)cos_sin.size(0), \
-      apply_rope ? 1 : 0, (int64_t)k_cache.size(0) * BS, inv_k, inv_v)
+#define LAUNCH_F(DD, TT, FF) \
+  rope_cache_kernel<DD, TT, FF><<<grid, 256, 0, stream>>>((bf16*)qkv.data_ptr(), kw, T, apply_rope ? 1 : 0)
 #define LAUNCH(DD, TT) \
   if (f8) LAUNCH_F(DD, TT, true); else LAUNCH_F(DD, TT, false)
   if (D == 128) { if (small) { LAUNCH(128, TOK_SMALL); } else { LAUNCH(128, TOK_LARGE); } }
