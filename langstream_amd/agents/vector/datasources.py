@@ -35,7 +35,7 @@ import sqlite3
 import threading
 from typing import Any, Dict, List, Optional, Sequence
 
-from ...engine.vector_store import VectorStoreRegistry
+from ...engine.vector_store import IdSet, VectorStoreRegistry
 
 log = logging.getLogger(__name__)
 
@@ -139,7 +139,9 @@ class LocalVectorDataSource(DataSource):
         return self.fetch_data_batch(query, [params])[0]
 
     def fetch_data_batch(self, query, params_list):
-        """Many queries of the same shape -> ONE kNN kernel launch per collection."""
+        """Many queries of the same shape -> ONE kNN kernel launch per collection; every
+        query's ``filter`` goes down to the store (per-query row masks), so queries with
+        different filters share the launch and get the exact top-k of the rows they admit."""
         parsed = [_bind_json(query, p) if isinstance(query, str) else query for p in params_list]
         out: List[Any] = [None] * len(parsed)
         groups: Dict[tuple, List[int]] = {}
@@ -148,26 +150,22 @@ class LocalVectorDataSource(DataSource):
                 raise ValueError("local vector query needs a 'vector'")
             coll = q.get("collection-name") or q.get("collection") or self.default_collection
             k = int(q.get("top-k", q.get("topK", q.get("limit", 10))))
-            flt = q.get("filter") or {}
-            key = (coll, k, json.dumps(flt, sort_keys=True), bool(q.get("include-vector", False)))
-            groups.setdefault(key, []).append(i)
+            groups.setdefault((coll, k, bool(q.get("include-vector", False))), []).append(i)
         from ...engine import dist_knn
         sharded = dist_knn.active()   # DP replicas: global top-k over every rank's shard
-        for (coll, k, flt_s, inc), idxs in groups.items():
+        for (coll, k, inc), idxs in groups.items():
             if sharded is None and not VectorStoreRegistry.exists(coll):
                 for i in idxs:
                     out[i] = []
                 continue
-            flt = json.loads(flt_s)
-            over = k if not flt else k * 4
             vecs = [parsed[i]["vector"] for i in idxs]
+            flts = [parsed[i].get("filter") or None for i in idxs]
+            flts = flts if any(f is not None for f in flts) else None
             if sharded is not None:
-                res = sharded.search(coll, vecs, over, with_vectors=inc).result()
+                res = sharded.search(coll, vecs, k, with_vectors=inc, filter=flts).result()
             else:
-                res = self._store(coll).search(vecs, over, with_vectors=inc)
+                res = self._store(coll).search(vecs, k, with_vectors=inc, filter=flts)
             for i, rows in zip(idxs, res):
-                if flt:
-                    rows = [r for r in rows if all(r.get(f) == v for f, v in flt.items())]
                 out[i] = rows[:k]
         return out
 
@@ -251,7 +249,7 @@ class SqliteDataSource(DataSource):
 
     def fetch_data(self, query, params):
         m = _KNN.match(query)
-        if m and not m.group("where"):
+        if m:
             table, col, k = m.group("table"), m.group("col"), int(m.group("k"))
             name = self._store_name(table, col)
             vec = params[-1]
@@ -259,7 +257,15 @@ class SqliteDataSource(DataSource):
                 vec = json.loads(vec)
             self._ensure_mirror(table, col, len(vec))
             store = VectorStoreRegistry.get(name, persist=False)
-            hits = store.search([vec], k)[0] if len(store) else []
+            flt = None
+            if m.group("where"):
+                # the WHERE clause picks the candidate rows in SQLite (its placeholders come
+                # before the vector's); the GPU mirror ranks exactly those rowids
+                with self.lock:
+                    cur = self.conn.execute(f"SELECT rowid FROM {table} {m.group('where')}",
+                                            [self._sql_param(p) for p in params[:-1]])
+                    flt = IdSet(r[0] for r in cur.fetchall())
+            hits = store.search([vec], k, filter=flt)[0] if len(store) and k > 0 else []
             if not hits:
                 return []
             ids = [h["id"] for h in hits]

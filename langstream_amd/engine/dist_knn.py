@@ -10,11 +10,14 @@ reference's shared database (VEC/QueryVectorDBAgent.java:27-93 over one datasour
 rounds (every rank takes part in every round, so collectives always match):
 
 1. all-gather of a small JSON header (gloo, CPU): each rank's pending requests
-   ``(collection, n_queries, k, include_vector, dim)`` and its stop flag; an empty round
-   sleeps ``tick`` and repeats;
+   ``(collection, n_queries, k, include_vector, dim, filters)`` and its stop flag; an empty
+   round sleeps ``tick`` and repeats.  ``filters`` is null, or the request's distinct
+   filters as canonical JSON plus one index per query (-1: unfiltered);
 2. per collection: all-gather of the query vectors ``[W*Qmax, d]`` over the data group
    (RCCL over xGMI on the GPU), the fused MFMA kNN kernel of the LOCAL shard on every
-   rank for all ``W*Qmax`` queries, then one all-to-all of ``(score, row)`` candidates
+   rank for all ``W*Qmax`` queries -- every rank compiles the round's distinct filters into
+   row masks of ITS shard, one mask row per filter and a mask index per gathered query, so
+   the launch stays one per collection -- then one all-to-all of ``(score, row)`` candidates
    ``[W, Qmax, k]`` back to the ranks that asked;
 3. merge on the device: top-k of the ``W*k`` candidates per query -> ``(owner, row)``;
 4. two-phase payload fetch over gloo: each rank asks every owner only for the rows in
@@ -41,7 +44,7 @@ import torch
 import torch.distributed as dist
 
 from ..utils.gpu import on_search, to_host
-from .vector_store import VectorStoreRegistry
+from .vector_store import VectorStoreRegistry, canonical_filter
 
 log = logging.getLogger(__name__)
 
@@ -68,10 +71,10 @@ def stop() -> None:
 
 
 class _Req:
-    __slots__ = ("coll", "q", "k", "inc", "fut")
+    __slots__ = ("coll", "q", "k", "inc", "flt", "fut")
 
-    def __init__(self, coll, q, k, inc):
-        self.coll, self.q, self.k, self.inc = coll, q, k, inc
+    def __init__(self, coll, q, k, inc, flt=None):
+        self.coll, self.q, self.k, self.inc, self.flt = coll, q, k, inc, flt
         self.fut: Future = Future()
 
 
@@ -117,12 +120,25 @@ class ShardedKnn:
         self._thread.start()
 
     # ------------------------------------------------------------------ client API
-    def search(self, collection: str, queries, k: int, with_vectors: bool = False) -> Future:
+    def search(self, collection: str, queries, k: int, with_vectors: bool = False, filter=None) -> Future:
         """Global top-k for the rows of ``queries`` ([Q, d]) -> Future[List[List[dict]]]
-        in the local store's result format (id, similarity, metadata[, vector])."""
+        in the local store's result format (id, similarity, metadata[, vector]).
+        ``filter``: as ``VectorStore.search`` -- one filter for all queries or one (or None)
+        per query; it is checked here, so a malformed filter fails only its own request."""
         q = np.array(queries.cpu() if isinstance(queries, torch.Tensor) else queries, dtype=np.float32, ndmin=2)
         q = q / np.maximum(np.linalg.norm(q, axis=-1, keepdims=True), 1e-12)
         r = _Req(collection, q, int(k), bool(with_vectors))
+        try:
+            per_q = filter if isinstance(filter, (list, tuple)) else [filter] * q.shape[0]
+            if len(per_q) != q.shape[0]:
+                raise ValueError(f"{len(per_q)} filters for {q.shape[0]} queries")
+            canon = [canonical_filter(f) for f in per_q]
+            if any(c is not None for c in canon):
+                distinct = sorted({c for c in canon if c is not None})
+                r.flt = [distinct, [-1 if c is None else distinct.index(c) for c in canon]]
+        except (ValueError, TypeError) as e:
+            r.fut.set_exception(e if isinstance(e, ValueError) else ValueError(str(e)))
+            return r.fut
         if r.k < 1:
             r.fut.set_exception(ValueError("top-k must be >= 1"))
             return r.fut
@@ -225,7 +241,8 @@ class ShardedKnn:
                         take.append(r)
                         n += r.q.shape[0]
                     stopping = self._stop and not take and not self._pending
-                hdr = {"s": stopping, "r": [[r.coll, int(r.q.shape[0]), r.k, r.inc, int(r.q.shape[1])] for r in take]}
+                hdr = {"s": stopping,
+                       "r": [[r.coll, int(r.q.shape[0]), r.k, r.inc, int(r.q.shape[1]), r.flt] for r in take]}
                 t_h = time.perf_counter()
                 hdrs = [json.loads(b) for b in self._allgather_bytes(json.dumps(hdr).encode())]
                 dt_h = time.perf_counter() - t_h
@@ -330,11 +347,28 @@ class ShardedKnn:
                         # LS_KNN_REPLICATE=R (diagnosis): search the gathered queries R times
                         # over, i.e. the per-round load of R x W ranks, and keep the first copy
                         qs = qall if self._replicate <= 1 else qall.repeat(self._replicate, 1)
+                        # the round's filters against THIS shard: one parsed object per
+                        # distinct filter, one reference per gathered query (None: padding
+                        # and unfiltered queries); the store turns them into mask rows
+                        flts: List[Any] = [None] * (W * qmax)
+                        parsed: Dict[str, Any] = {}
+                        for i in range(W):
+                            pos = i * qmax
+                            for hi, r in reqs_all:
+                                if hi != i:
+                                    continue
+                                if len(r) > 5 and r[5]:
+                                    for j, w in enumerate(r[5][1]):
+                                        if w >= 0:
+                                            c = r[5][0][w]
+                                            flts[pos + j] = parsed.setdefault(c, json.loads(c))
+                                pos += r[1]
+                        flts = flts * self._replicate
                         if store.device.type == "cuda" and self.data_dev.type == "cpu":
-                            s, idx = to_host(*store.topk_rows(qs.pin_memory().to(
-                                store.device, non_blocking=True).to(store.dtype), kmax))
+                            s, idx = to_host(*store.topk_filtered(qs.pin_memory().to(
+                                store.device, non_blocking=True).to(store.dtype), kmax, flts))
                         else:
-                            s, idx = store.topk_rows(qs.to(store.device, store.dtype), kmax)
+                            s, idx = store.topk_filtered(qs.to(store.device, store.dtype), kmax, flts)
                             s, idx = s.to(self.data_dev), idx.to(self.data_dev)
                         s, idx = s[: W * qmax], idx[: W * qmax]
                     except Exception as e:  # noqa: BLE001 - contribute nothing, keep the collectives

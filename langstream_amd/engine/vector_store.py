@@ -45,6 +45,101 @@ log = logging.getLogger(__name__)
 
 KERNEL_DIMS = (128, 256, 384, 512, 768, 1024, 1536, 2048)
 KERNEL_MAX_K = 64
+# Filtered search: a filter that admits at most this many rows is served by gathering the
+# admitted rows and searching the compact matrix unfiltered; above it the masked kernels
+# stream the whole store (docs/ARCHITECTURE.md "Filtered vector search" has the curve).
+# Measured crossover over 1M x 384: ~500k admitted rows, rounded down to a power of two.
+COMPACT_MAX = int(os.environ.get("LS_KNN_COMPACT_MAX", 262144))
+# The compact route is one gather + launch per distinct filter, the masked route one launch
+# for any mix: a batch with more distinct selective filters than this stays masked.
+COMPACT_FILTERS = 4
+MASK_CACHE_SIZE = 16
+
+_FIELD_OPS = ("$eq", "$ne", "$in", "$nin")
+
+
+class IdSet:
+    """A filter that admits the rows with the given store ids (``VectorStore.mask_from_ids``);
+    the SQL datasource passes the rowids its WHERE clause selected."""
+
+    __slots__ = ("ids",)
+
+    def __init__(self, ids):
+        self.ids = list(ids)
+
+
+def check_filter(flt) -> None:
+    """Raise ValueError for anything outside the filter grammar: top-level keys ANDed;
+    ``field: scalar`` (equality); ``field: {"$eq" | "$ne" | "$in" | "$nin": ...}``;
+    ``"$and": [...]`` / ``"$or": [...]``, nested."""
+    if not isinstance(flt, dict):
+        raise ValueError(f"a filter is a JSON object, not {type(flt).__name__}")
+    for key, val in flt.items():
+        if key in ("$and", "$or"):
+            if not isinstance(val, list):
+                raise ValueError(f"filter operator {key} takes a list of filters")
+            for sub in val:
+                check_filter(sub)
+        elif isinstance(key, str) and key.startswith("$"):
+            raise ValueError(f"unsupported filter operator {key}")
+        elif isinstance(val, dict) and any(isinstance(o, str) and o.startswith("$") for o in val):
+            for op, arg in val.items():
+                if op not in _FIELD_OPS:
+                    raise ValueError(f"unsupported filter operator {op} on field {key!r}")
+                if op in ("$in", "$nin") and not isinstance(arg, list):
+                    raise ValueError(f"filter operator {op} on field {key!r} takes a list")
+
+
+def canonical_filter(flt) -> Optional[str]:
+    """The cache / wire form of a filter: None for "no filter", else its canonical JSON."""
+    if flt is None or flt == {}:
+        return None
+    check_filter(flt)
+    return json.dumps(flt, sort_keys=True, separators=(",", ":"))
+
+
+def pack_mask(adm: np.ndarray) -> np.ndarray:
+    """bool [n] -> int32 [32 * ceil(n / 1024)]: bit b of word w admits row 32w + b, zero
+    bits up to a whole number of 1024-row chunks (the kernels never bounds-check a read)."""
+    n = adm.shape[0]
+    bits = np.zeros(max(1, (n + 1023) // 1024) * 1024, dtype=bool)
+    bits[:n] = adm
+    return np.packbits(bits, bitorder="little").view(np.int32)
+
+
+class _CodeColumn:
+    """One metadata field (or ``id``) as integer value codes, one per row: -1 the row has
+    no such key, -2 its value is unhashable (compared row by row), else ``code_of[value]``."""
+
+    MISSING, NOCODE = -1, -2
+
+    def __init__(self, cap: int):
+        self.codes = np.full(max(16, cap), self.MISSING, dtype=np.int64)
+        self.code_of: Dict[Any, int] = {}
+
+    def ensure(self, n: int) -> None:
+        if n > self.codes.shape[0]:
+            grown = np.full(max(n, 2 * self.codes.shape[0]), self.MISSING, dtype=np.int64)
+            grown[: self.codes.shape[0]] = self.codes
+            self.codes = grown
+
+    def code(self, present: bool, value) -> int:
+        if not present:
+            return self.MISSING
+        try:
+            c = self.code_of.get(value)
+            if c is None:
+                c = self.code_of[value] = len(self.code_of)
+            return c
+        except TypeError:
+            return self.NOCODE
+
+    def lookup(self, value) -> Optional[int]:
+        """The code of ``value``; None when no row holds it; NOCODE when it is unhashable."""
+        try:
+            return self.code_of.get(value)
+        except TypeError:
+            return self.NOCODE
 
 
 def _safe(name: str) -> str:
@@ -230,6 +325,12 @@ class VectorStore:
         self.lock = threading.RLock()
         self._write_ev = None   # recorded on the store stream after every device write
         self._gen = 0           # bumped when deletes renumber rows (search re-resolves)
+        self._mut = 0           # bumped by every upsert and delete (cached masks are per value)
+        self._cols: Dict[str, _CodeColumn] = {}   # code columns of the fields filters have used
+        self._masks: Dict[str, Dict[str, Any]] = {}   # canonical filter -> mask entry (LRU)
+        self._masks_mut = 0
+        self.compact_max = COMPACT_MAX
+        self.filter_stats = {"compact": 0, "masked": 0, "mask_builds": 0}
         self.search_retries = 0
         self._persist = _Persistence(persist_dir, fsync) if persist_dir else None
         if self._persist is not None:
@@ -334,6 +435,11 @@ class VectorStore:
             else:
                 self._meta[r] = md
             rows.append(r)
+        self._mut += 1
+        for field, col in self._cols.items():
+            col.ensure(self._n)
+            for k, md, r in zip(ids, metadata, rows):
+                col.codes[r] = col.code(True, k) if field == "id" else col.code(field in md, md.get(field))
         # duplicate ids in one batch: the last occurrence wins (index_copy_ order is unspecified)
         last: Dict[int, int] = {}
         for j, r in enumerate(rows):
@@ -358,6 +464,7 @@ class VectorStore:
     def _apply_delete(self, ids) -> int:
         """Remove rows in one device copy: the surviving tail rows fill the holes."""
         self._gen += 1   # row numbers change: a search between its top-k and its payloads redoes
+        self._mut += 1
         dead = {self._row.pop(k) for k in ids}
         m = len(dead)
         keep_n = self._n - m
@@ -371,6 +478,8 @@ class VectorStore:
                 self._ids[h] = self._ids[f]
                 self._meta[h] = self._meta[f]
                 self._row[self._ids[h]] = h
+            for col in self._cols.values():   # the code columns move with the rows
+                col.codes[holes] = col.codes[fillers]
         del self._ids[keep_n:]
         del self._meta[keep_n:]
         self._n = keep_n
@@ -442,11 +551,183 @@ class VectorStore:
             with on_search(self.device):
                 return to_host(self._vecs[r].float())[0].tolist()
 
+    # ------------------------------------------------------------------ filters
+    # Everything here runs with ``lock`` held: a mask is only meaningful for the row
+    # numbering it was built against, so it is built and its top-k enqueued in one locked
+    # section (``topk_filtered``).
+    def _column(self, field: str) -> _CodeColumn:
+        col = self._cols.get(field)
+        if col is None:   # first filter on this field: one pass over the rows, maintained from then on
+            col = _CodeColumn(len(self._ids))
+            if field == "id":
+                for r, key in enumerate(self._ids):
+                    col.codes[r] = col.code(True, key)
+            else:
+                for r, md in enumerate(self._meta):
+                    col.codes[r] = col.code(field in md, md.get(field))
+            self._cols[field] = col
+        return col
+
+    def _eq(self, field: str, value) -> np.ndarray:
+        col = self._column(field)
+        codes = col.codes[: self._n]
+        c = col.lookup(value)
+        if c is None:
+            return np.zeros(self._n, dtype=bool)
+        if c != _CodeColumn.NOCODE:
+            return codes == c
+        out = np.zeros(self._n, dtype=bool)   # an unhashable value (list, object): row by row
+        for r in np.flatnonzero(codes == _CodeColumn.NOCODE).tolist():
+            out[r] = (self._ids[r] if field == "id" else self._meta[r].get(field)) == value
+        return out
+
+    def _admitted(self, flt: Dict[str, Any]) -> np.ndarray:
+        """bool [n]: the rows ``flt`` admits (numpy comparisons over the code columns)."""
+        out = np.ones(self._n, dtype=bool)
+        for key, val in flt.items():
+            if key == "$and":
+                for sub in val:
+                    out &= self._admitted(sub)
+            elif key == "$or":
+                acc = np.zeros(self._n, dtype=bool)
+                for sub in val:
+                    acc |= self._admitted(sub)
+                out &= acc
+            elif isinstance(val, dict) and any(isinstance(o, str) and o.startswith("$") for o in val):
+                for op, arg in val.items():
+                    if op in ("$eq", "$ne"):
+                        m = self._eq(key, arg)
+                    else:
+                        m = np.zeros(self._n, dtype=bool)
+                        for a in arg:
+                            m |= self._eq(key, a)
+                    out &= m if op in ("$eq", "$in") else ~m   # a missing key matches only $ne / $nin
+            else:
+                out &= self._eq(key, val)
+        return out
+
+    def mask_from_ids(self, ids) -> np.ndarray:
+        """bool [n]: the rows holding the given store ids (unknown ids admit nothing)."""
+        out = np.zeros(self._n, dtype=bool)
+        rows = [r for r in (self._row.get(i) for i in ids) if r is not None]
+        if rows:
+            out[np.asarray(rows, dtype=np.int64)] = True
+        return out
+
+    def _upload(self, a: np.ndarray) -> torch.Tensor:
+        t = torch.from_numpy(a)
+        if self.device.type == "cuda":
+            t = t.pin_memory().to(self.device, non_blocking=True)
+        return t
+
+    def _mask_entry(self, flt) -> Dict[str, Any]:
+        """{"count": admitted rows, "adm": host bool [n]} of one filter, plus its device forms
+        once a route has asked for them (``_entry_mask`` / ``_entry_rows``); JSON filters are
+        cached until the next mutation."""
+        if self._masks_mut != self._mut:
+            self._masks.clear()
+            self._masks_mut = self._mut
+        key = None if isinstance(flt, IdSet) else canonical_filter(flt)
+        e = self._masks.get(key) if key is not None else None
+        if e is not None:
+            self._masks[key] = self._masks.pop(key)   # most recently used last
+            return e
+        adm = self.mask_from_ids(flt.ids) if isinstance(flt, IdSet) else self._admitted(flt)
+        self.filter_stats["mask_builds"] += 1
+        e = {"count": int(adm.sum()), "adm": adm}
+        if key is not None:
+            self._masks[key] = e
+            while len(self._masks) > MASK_CACHE_SIZE:
+                self._masks.pop(next(iter(self._masks)))
+        return e
+
+    def _entry_mask(self, e) -> torch.Tensor:
+        """device int32 [1, W]: the filter as a kernel mask row (one pinned upload)."""
+        if "mask" not in e:
+            e["mask"] = self._upload(pack_mask(e["adm"])[None])
+        return e["mask"]
+
+    def _entry_rows(self, e) -> torch.Tensor:
+        """device int64 [count]: the admitted row numbers, ascending."""
+        if "rows" not in e:
+            e["rows"] = self._upload(np.flatnonzero(e["adm"]).astype(np.int64))
+        return e["rows"]
+
+    def topk_filtered(self, q: torch.Tensor, k: int, filters: Sequence[Any]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``topk_rows`` with one filter (a filter object, an ``IdSet`` or None) per query
+        (caller holds ``lock`` from here until the rows are resolved or the generation is
+        checked).  Queries whose filter admits at most ``compact_max`` rows search a gathered
+        copy of those rows; the others share one masked launch with the unfiltered ones."""
+        Qn, n = q.shape[0], self._n
+        if n == 0 or Qn == 0 or all(f is None for f in filters):
+            return self.topk_rows(q, k)
+        if len(filters) != Qn:
+            raise ValueError(f"{len(filters)} filters for {Qn} queries")
+        entries: List[Dict[str, Any]] = []
+        seen: Dict[int, int] = {}
+        which = []
+        for f in filters:
+            if f is None or f == {}:
+                which.append(-1)
+                continue
+            j = seen.get(id(f))
+            if j is None:
+                e = self._mask_entry(f)
+                j = next((i for i, o in enumerate(entries) if o is e), None)
+                if j is None:
+                    j = len(entries)
+                    entries.append(e)
+                seen[id(f)] = j
+            which.append(j)
+        compact = [j for j, e in enumerate(entries) if e["count"] <= self.compact_max]
+        if len(compact) > COMPACT_FILTERS:
+            compact = []
+        mrow, masks = {}, []
+        for j, e in enumerate(entries):
+            if j not in compact:
+                mrow[j] = len(masks)
+                masks.append(self._entry_mask(e))
+        if not compact:
+            self.filter_stats["masked"] += 1
+            return self.topk_rows(q, k, masks[0] if len(masks) == 1 else torch.cat(masks),
+                                  [mrow.get(j, -1) for j in which])
+        out_s = torch.full((Qn, k), float("-inf"), device=self.device)
+        out_i = torch.full((Qn, k), -1, device=self.device, dtype=torch.int32)
+        rest = [i for i, j in enumerate(which) if j not in compact]
+        if rest:
+            sel = torch.tensor(rest, device=self.device)
+            if masks:
+                self.filter_stats["masked"] += 1
+                s, i = self.topk_rows(q[sel], k, masks[0] if len(masks) == 1 else torch.cat(masks),
+                                      [mrow.get(which[r], -1) for r in rest])
+            else:
+                s, i = self.topk_rows(q[sel], k)
+            out_s[sel], out_i[sel] = s, i
+        self._order_read()
+        for j in compact:
+            if entries[j]["count"] == 0:
+                continue
+            rows = self._entry_rows(entries[j])
+            self.filter_stats["compact"] += 1
+            sel = torch.tensor([i for i, w in enumerate(which) if w == j], device=self.device)
+            Xc = self._vecs.index_select(0, rows)
+            if self.device.type == "cuda" and self.kernel_dim and k <= KERNEL_MAX_K:
+                s, i = ops.knn_topk(Xc, q[sel].contiguous(), k)
+            else:
+                s, i = _exact_topk(Xc, q[sel], k)
+            # compact indices ascend with the row numbers, so ties still go to the lower row
+            out_s[sel] = s
+            out_i[sel] = torch.where(i >= 0, rows[i.clamp_min(0).long()].int(), i)
+        return out_s, out_i
+
     # ------------------------------------------------------------------ search
-    def topk_rows(self, q: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    def topk_rows(self, q: torch.Tensor, k: int, mask: Optional[torch.Tensor] = None,
+                  qmask=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Device top-k over the live rows (caller holds ``lock``; any stream -- the read
         is ordered after the store's last write).  q: normalised [Q, dim] in the store dtype.  Returns (scores f32 [Q,k],
-        rows int32 [Q,k]); missing entries are (-inf, -1)."""
+        rows int32 [Q,k]); missing entries are (-inf, -1).  ``mask`` (device int32
+        [M, 32 * ceil(n / 1024)], ``pack_mask`` rows) and ``qmask`` (host list / tensor [Q]:
+        mask row per query, -1 = none) restrict each query to the rows its mask admits."""
         n = self._n
         Qn = q.shape[0]
         if n == 0 or Qn == 0:
@@ -455,12 +736,26 @@ class VectorStore:
         self._order_read()
         X = self._vecs[:n]
         if self.device.type == "cuda" and self.kernel_dim and k <= KERNEL_MAX_K:
-            return ops.knn_topk(X, q.contiguous(), k)
-        return _exact_topk(X, q, k)
+            return ops.knn_topk(X, q.contiguous(), k, mask=mask, qmask=qmask)
+        return _exact_topk(X, q, k, mask=mask, qmask=qmask)
 
-    def search(self, queries, k: int = 10, with_vectors: bool = False) -> List[List[Dict[str, Any]]]:
+    def _query_filters(self, filter, Qn: int) -> Optional[List[Any]]:
+        """``search``'s filter argument as one entry per query (None: no query is filtered)."""
+        per_query = filter if isinstance(filter, (list, tuple)) else [filter] * Qn
+        if len(per_query) != Qn:
+            raise ValueError(f"{len(per_query)} filters for {Qn} queries")
+        out = []
+        for f in per_query:
+            if f is not None and not isinstance(f, IdSet):
+                check_filter(f)
+            out.append(None if f is None or f == {} else f)
+        return out if any(f is not None for f in out) else None
+
+    def search(self, queries, k: int = 10, with_vectors: bool = False, filter=None) -> List[List[Dict[str, Any]]]:
         """queries: [Q, dim] (list or tensor).  Returns per query a list of
-        {"id", "similarity", **metadata} sorted by decreasing cosine similarity."""
+        {"id", "similarity", **metadata} sorted by decreasing cosine similarity.
+        ``filter``: one filter for all queries or a list with one filter or None per query
+        (grammar: ``check_filter``); each query gets the exact top-k of the rows it admits."""
         if k < 1:
             raise ValueError("top-k must be >= 1")
         tr = SEARCH_TRACE
@@ -470,6 +765,8 @@ class VectorStore:
         # 26 ms per round in the RAG bench where this one took 30-170 ms per batch:
         # profiles/r5/bench_stage_trace_r5j.log vs knn_w8load_r5o.log)
         qn = self._normalize_host(queries)
+        filters = self._query_filters(filter, qn.shape[0])
+        topk = self.topk_rows if filters is None else (lambda q_, k_: self.topk_filtered(q_, k_, filters))
         # The lock is held while work is ENQUEUED, not while the GPU runs it: the top-k and
         # its D2H copy are enqueued under the lock and waited for outside it; the row
         # numbers are then resolved under the lock again, unless a delete renumbered the
@@ -484,7 +781,7 @@ class VectorStore:
                     # search always finishes
                     with self.lock:
                         t_lk = time.time() if tr is not None else 0.0
-                        (hs, hi), ev = to_host_async(*self.topk_rows(q, k))
+                        (hs, hi), ev = to_host_async(*topk(q, k))
                         if ev is not None:
                             ev.synchronize()
                         s, idx = hs.tolist(), hi.tolist()
@@ -497,7 +794,7 @@ class VectorStore:
                 with self.lock:
                     t_lk = time.time() if tr is not None else 0.0
                     gen = self._gen
-                    (hs, hi), ev = to_host_async(*self.topk_rows(q, k))
+                    (hs, hi), ev = to_host_async(*topk(q, k))
                 if ev is not None:
                     ev.synchronize()
                 s, idx = hs.tolist(), hi.tolist()
@@ -609,14 +906,23 @@ class VectorStore:
         return flat, arr
 
 
-def _exact_topk(X: torch.Tensor, q: torch.Tensor, k: int, chunk: int = 1 << 20):
-    """Exact top-k by chunked GEMM + torch.topk (dims / k outside the kernel)."""
+def _exact_topk(X: torch.Tensor, q: torch.Tensor, k: int, chunk: int = 1 << 20, mask=None, qmask=None):
+    """Exact top-k by chunked GEMM + torch.topk (dims / k outside the kernel, CPU stores).
+    mask / qmask as in ``ops.knn_topk``: rows a query's mask rejects score -inf."""
     Qn = q.shape[0]
     best_s = torch.full((Qn, 0), float("-inf"), device=X.device)
     best_i = torch.full((Qn, 0), -1, device=X.device, dtype=torch.long)
     qf = q.float()
+    if mask is not None:
+        qm = torch.as_tensor(qmask, dtype=torch.long).to(X.device)
+        if qm.numel() != Qn or mask.shape[1] * 32 < X.shape[0] or int(qm.max()) >= mask.shape[0]:
+            raise ValueError("kNN mask / qmask do not fit the store and the queries")
     for s0 in range(0, X.shape[0], chunk):
         sc = qf @ X[s0: s0 + chunk].float().t()
+        if mask is not None:
+            rows = torch.arange(s0, s0 + sc.shape[1], device=X.device)
+            bits = ((mask[:, rows >> 5] >> (rows & 31).int()) & 1).bool()          # [M, rows]
+            sc = sc.masked_fill(~(bits[qm.clamp_min(0)] | (qm < 0)[:, None]), float("-inf"))
         kk = min(k, sc.shape[1])
         v, i = torch.topk(sc, kk, dim=-1)
         best_s = torch.cat([best_s, v], 1)
@@ -628,6 +934,8 @@ def _exact_topk(X: torch.Tensor, q: torch.Tensor, k: int, chunk: int = 1 << 20):
         pad = k - best_s.shape[1]
         best_s = torch.cat([best_s, best_s.new_full((Qn, pad), float("-inf"))], 1)
         best_i = torch.cat([best_i, best_i.new_full((Qn, pad), -1)], 1)
+    if mask is not None:
+        best_i = best_i.masked_fill(best_s == float("-inf"), -1)
     return best_s, best_i.int()
 
 

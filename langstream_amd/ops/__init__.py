@@ -496,10 +496,72 @@ def l2_normalize_rows(x):
     return torch.nn.functional.normalize(x.float(), dim=-1, eps=1e-12).to(x.dtype)
 
 
-def knn_topk(X, Q, k: int, sample_chunks: Optional[int] = None, _ablate: int = 0):
+def _knn_check_mask(X, Q, mask, qmask) -> torch.Tensor:
+    """Validate a kNN row mask and its per-query selector; returns qmask as a host int32
+    tensor.  After this no mask read of the kernels can leave ``mask``: every selector is
+    -1 or a mask row, and every mask row covers whole 1024-row chunks of X."""
+    if mask is None or qmask is None:
+        raise ValueError("knn_topk: mask and qmask go together")
+    nchunks = (X.shape[0] + 1023) // 1024
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32:
+        raise ValueError("knn_topk: mask must be an int32 tensor")
+    if mask.dim() != 2 or mask.shape[1] != 32 * nchunks:
+        raise ValueError(f"knn_topk: mask must be [M, {32 * nchunks}] for {X.shape[0]} rows, got {tuple(mask.shape)}")
+    if mask.device != X.device or not mask.is_contiguous():
+        raise ValueError("knn_topk: mask must be contiguous and on the device of X")
+    if isinstance(qmask, torch.Tensor):
+        if qmask.is_cuda:
+            raise ValueError("knn_topk: qmask is a host tensor or a list (it is validated before upload)")
+        if qmask.dtype not in (torch.int32, torch.int64):
+            raise ValueError("knn_topk: qmask must be int32 or int64")
+        qm = qmask.to(torch.int32)
+    else:
+        qm = torch.tensor(list(qmask), dtype=torch.int64)
+    if qm.dim() != 1 or qm.numel() != Q.shape[0]:
+        raise ValueError(f"knn_topk: qmask must have one entry per query ({Q.shape[0]}), got {tuple(qm.shape)}")
+    if qm.numel() and (int(qm.min()) < -1 or int(qm.max()) >= mask.shape[0]):
+        raise ValueError(f"knn_topk: qmask values must lie in [-1, {mask.shape[0]})")
+    return qm.to(torch.int32).contiguous()
+
+
+def _knn_topk_masked(X, Q, k: int, sample_chunks: Optional[int], mask, qm):
+    Qn, N = Q.shape[0], X.shape[0]
+    nchunks = (N + 1023) // 1024
+    dev = X.device
+    out_s = torch.empty(Qn, k, dtype=torch.float32, device=dev)
+    out_i = torch.empty(Qn, k, dtype=torch.int32, device=dev)
+    if N == 0 or Qn == 0:
+        return out_s.fill_(float("-inf")), out_i.fill_(-1)
+    if sample_chunks is None:
+        sample_chunks = 16 if Qn >= 1024 else 32
+    ws_s = torch.empty(max(1, Qn * nchunks * k), dtype=torch.float32, device=dev)
+    ws_i = torch.empty(Qn * nchunks * k + 3 * Qn, dtype=torch.int32, device=dev)
+    qd = (qm.pin_memory() if dev.type == "cuda" else qm).to(dev, non_blocking=True)
+    hip().knn_topk_masked(X, Q, k, out_s, out_i, ws_s, ws_i, sample_chunks, mask, qd)
+    if sample_chunks > 0 and nchunks > sample_chunks and bool(ws_i[-Qn:].any()):
+        # a candidate list overflowed (a mask that admits few sample rows leaves a weak
+        # threshold): exact rerun
+        hip().knn_topk_masked(X, Q, k, out_s, out_i, ws_s, ws_i, 0, mask, qd)
+    return out_s, out_i
+
+
+def knn_topk(X, Q, k: int, sample_chunks: Optional[int] = None, mask=None, qmask=None, _ablate: int = 0):
     """Top-k rows of X by dot product with each query row.  Returns (scores f32 [Q,k], idx int32 [Q,k]).
     GPU: the first ``sample_chunks`` x 1024 rows are searched exactly and set a per-query
-    threshold for the rest (0 = search every chunk exactly); ties go to the lower row."""
+    threshold for the rest (0 = search every chunk exactly); ties go to the lower row.
+
+    ``mask`` (int32 [M, 32 * ceil(N / 1024)], bit b of word w = row 32w + b, zero bits
+    past N) and ``qmask`` (host int32 [Q] or list: each query's mask row, -1 = no filter)
+    restrict every query to the rows its mask admits; a query with fewer than k admitted
+    rows pads with (-inf, -1)."""
+    if mask is not None or qmask is not None:
+        qm = _knn_check_mask(X, Q, mask, qmask)
+        if _ablate:
+            raise ValueError("knn_topk: the timing ablations take no mask")
+        if not _gpu(X):
+            return ref.knn_topk(X, Q, k, mask, qm)
+        if bool((qm >= 0).any()):
+            return _knn_topk_masked(X, Q, k, sample_chunks, mask, qm)
     if _gpu(X):
         Qn, N = Q.shape[0], X.shape[0]
         nchunks = (N + 1023) // 1024

@@ -19,6 +19,11 @@
 //
 // Scores are raw dot products; the store keeps rows L2-normalised so this is
 // cosine similarity.  Rows >= N (tail chunk) score -inf.
+//
+// Filtered search (knn_topk_masked): every query may name a row mask; a row its mask
+// rejects scores -inf in the exact kernel and is never appended by the main-pass kernels,
+// so the answer is the exact top-k of the admitted rows, padded with (-inf, -1) when fewer
+// than k are admitted (see knn_admitted).  The unmasked instantiations are unchanged.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "ops.h"
@@ -58,12 +63,22 @@ __device__ __forceinline__ void wave_sort_desc(float& v, int& i, int lane) {
   }
 }
 
-template <int DIM>
+// Row masks (MASKED instantiations; the unmasked ones compile to what they were without
+// the parameter): mask is int32 [M, mw], mw = 32 * nchunks_total words -- bit b of word w
+// admits row 32w + b, every mask row padded with zero bits to whole 1024-row chunks, so a
+// read for any row of any chunk stays inside its mask row.  qmask[q] is query q's mask row,
+// -1 = every row admitted.  The host validates both before a launch (ops.knn_topk).
+__device__ __forceinline__ bool knn_admitted(const int32_t* __restrict__ mask, int mw, int mrow, int64_t row) {
+  return mrow < 0 || (((uint32_t)mask[(int64_t)mrow * mw + (row >> 5)] >> (row & 31)) & 1u);
+}
+
+template <int DIM, bool MASKED = false>
 __global__ void __launch_bounds__(256) knn_exact_kernel(const bf16* __restrict__ X, int64_t N,
                                                          const bf16* __restrict__ Qm, int Qn, int K,
                                                          float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
                                                          int* __restrict__ ctrl, int nchunks_total, int chunk0,
-                                                         int nchunks) {
+                                                         int nchunks, const int32_t* __restrict__ mask,
+                                                         const int32_t* __restrict__ qmask) {
   constexpr int KS = DIM / 32;
   constexpr int QROW = DIM + 8;   // +16 B per query row: the 16 lanes i16 of a B-fragment read hit distinct banks
   constexpr int KB = KS < 32 ? KS : 32;   // k-steps per load batch (DIM 2048: two batches)
@@ -94,8 +109,22 @@ __global__ void __launch_bounds__(256) knn_exact_kernel(const bf16* __restrict__
   }
   __syncthreads();
   const int64_t row0 = (int64_t)chunk * CH + wid * 256;
+  // MASKED: this lane's query (column i16) reads one mask word per two 16-row subtiles --
+  // word 8 * wid + st / 2 of the chunk's 32, rows 4h + rr of subtile st at bits
+  // 16 * (st & 1) + 4h + rr.  Queries past Qn are never selected from: no filter.
+  const int32_t* mwp = nullptr;
+  if constexpr (MASKED) {
+    const int qi = qg * QG + i16;
+    const int mrow = qi < Qn ? qmask[qi] : -1;
+    if (mrow >= 0) mwp = mask + (int64_t)mrow * (32 * (int64_t)nchunks_total) + (int64_t)chunk * 32 + wid * 8;
+  }
   for (int st0 = 0; st0 < 16; st0 += U) {
     f32x4 acc[U];
+    uint32_t mword[(U + 1) / 2];
+    if constexpr (MASKED) {
+#pragma unroll
+      for (int j = 0; j < (U + 1) / 2; ++j) mword[j] = mwp ? (uint32_t)mwp[st0 / 2 + j] : 0xFFFFFFFFu;
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -123,7 +152,9 @@ __global__ void __launch_bounds__(256) knn_exact_kernel(const bf16* __restrict__
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
         const int lr = wid * 256 + (st0 + u) * 16 + 4 * h + rr;
-        sc[i16][lr] = row0 + (st0 + u) * 16 + 4 * h + rr < N ? acc[u][rr] : -INFINITY;
+        bool ok = row0 + (st0 + u) * 16 + 4 * h + rr < N;
+        if constexpr (MASKED) ok = ok && ((mword[u / 2] >> (16 * ((st0 + u) & 1) + 4 * h + rr)) & 1u);
+        sc[i16][lr] = ok ? acc[u][rr] : -INFINITY;
       }
   }
   __syncthreads();
@@ -241,12 +272,13 @@ __global__ void __launch_bounds__(256) knn_exact_kernel(const bf16* __restrict__
 // sample is the lowest rows.  A list that fills up (adversarial data: many rows above
 // the sample's K-th best) sets the query's overflow flag; the host then reruns the
 // search exactly.
-template <int DIM>
+template <int DIM, bool MASKED = false>
 __global__ void __launch_bounds__(256) knn_filter_kernel(const bf16* __restrict__ X, int64_t N,
                                                          const bf16* __restrict__ Qm, int Qn,
                                                          float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
                                                          int* __restrict__ ctrl, int64_t cap, int chunk0,
-                                                         int nchunks) {
+                                                         int nchunks, const int32_t* __restrict__ mask,
+                                                         const int32_t* __restrict__ qmask, int mw) {
   constexpr int KS = DIM / 32;
   constexpr int QROW = DIM + 8;
   constexpr int KB = KS < 32 ? KS : 32;
@@ -271,6 +303,14 @@ __global__ void __launch_bounds__(256) knn_filter_kernel(const bf16* __restrict_
   for (int g = 0; g < QF / 16; ++g) {
     const int qi = qf * QF + 16 * g + i16;
     thr[g] = qi < Qn ? key2f(ctrl[Qn + qi]) : INFINITY;
+  }
+  int mrow[QF / 16];   // MASKED: each query's mask row (-1: every row admitted)
+  if constexpr (MASKED) {
+#pragma unroll
+    for (int g = 0; g < QF / 16; ++g) {
+      const int qi = qf * QF + 16 * g + i16;
+      mrow[g] = qi < Qn ? qmask[qi] : -1;
+    }
   }
   __syncthreads();
   const int64_t row0 = (int64_t)chunk * CH + wid * 256;
@@ -311,6 +351,9 @@ __global__ void __launch_bounds__(256) knn_filter_kernel(const bf16* __restrict_
         for (int rr = 0; rr < 4; ++rr) {
           const int64_t row = row0 + (st0 + u) * 16 + 4 * h + rr;
           if (acc[u][g][rr] > thr[g] && row < N) {
+            // the mask word is read only for scores that already passed the threshold
+            if constexpr (MASKED)
+              if (!knn_admitted(mask, mw, mrow[g], row)) continue;
             const int qi = qf * QF + 16 * g + i16;
             const int slot = __hip_atomic_fetch_add(ctrl + qi, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (slot < cap) {
@@ -361,13 +404,20 @@ __global__ void __launch_bounds__(256) knn_filter_kernel(const bf16* __restrict_
 // wave per SIMD nothing covers a wave's waits (profiles/knn_nw_r4v/).
 // ABL (timing-only diagnosis, wrong results): 1 drops the in-loop vmcnt wait + barrier,
 // 2 also the LDS-DMA issue, 3 drops the MFMAs instead.
-template <int DIM, int MODE, int NW = 8, int ABL = 0>
+// MASKED (MODE 0 only): a candidate's mask bit is tested in flush(), where the wave's global
+// traffic already is, so the tile loop stays free of returning global operations.  The
+// other place, the hit path of epi, measured slower wherever this kernel serves a filter
+// (Q = 256 over 1M x 384, admitted 0.5 / 0.25 / 0.1: 0.457 / 0.463 / 0.489 ms here against
+// 0.501 / 0.529 / 0.554; profiles/r7/knn_filter/); it won only at 0.001 (0.69 vs 0.97 ms:
+// rejected hits never reach the LDS buffers), where the store gathers the rows instead.
+template <int DIM, int MODE, int NW = 8, int ABL = 0, bool MASKED = false>
 __global__ void __launch_bounds__(NW * 64, 1) knn_filter_q256_kernel(const bf16* __restrict__ X, int64_t N,
                                                               const bf16* __restrict__ Qm, int Qn,
                                                               float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
                                                               int* __restrict__ ctrl, int64_t cap, int64_t row_begin,
                                                               int rows_per_wg, int nqb, float* __restrict__ gmax,
-                                                              int G, int prio) {
+                                                              int G, int prio, const int32_t* __restrict__ mask,
+                                                              const int32_t* __restrict__ qmask, int mw) {
   constexpr int KS = DIM / 32;
   constexpr int RB = DIM * 2;                    // bytes per row
   constexpr int TR = 64;                         // rows per LDS stage
@@ -400,6 +450,8 @@ __global__ void __launch_bounds__(NW * 64, 1) knn_filter_q256_kernel(const bf16*
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     for (int e = lane; e < ccount; e += 64) {
       const int qi = c_q[e];
+      if constexpr (MASKED)
+        if (!knn_admitted(mask, mw, qmask[qi], c_r[e])) continue;
       const int slot = __hip_atomic_fetch_add(ctrl + qi, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (slot < cap) {
         cand_s[(int64_t)qi * cap + slot] = c_s[e];
@@ -518,11 +570,11 @@ __global__ void __launch_bounds__(NW * 64, 1) knn_filter_q256_kernel(const bf16*
       for (int rr = 0; rr < 4; ++rr) {
         const int lr = sr0 + 4 * h + rr;
         const bool hit = pass(acc[g][rr], thr[g]) && lr < nrows;
-        const uint64_t mask = __ballot(hit);
-        if (mask == 0) continue;
-        const int nh = __popcll(mask);
+        const uint64_t hits = __ballot(hit);
+        if (hits == 0) continue;
+        const int nh = __popcll(hits);
         if (ccount + nh > CAPW) flush();   // rare: drains the DMA ring once
-        const int pos = ccount + __popcll(mask & ((1ull << lane) - 1ull));
+        const int pos = ccount + __popcll(hits & ((1ull << lane) - 1ull));
         if (hit) {
           c_s[pos] = acc[g][rr];
           c_r[pos] = (int)(r0 + lr);
@@ -662,30 +714,38 @@ __global__ void __launch_bounds__(256) knn_group_thr_kernel(const float* __restr
 
 template <int DD, int MM>
 void launch_q256(int abl, dim3 grid, hipStream_t stream, const bf16* X, int64_t N, const bf16* Q, int Qn, float* ws_s,
-                 int32_t* ws_i, int* ctrl, int64_t cap, int64_t row_begin, int rpw, int nqb, int G) {
+                 int32_t* ws_i, int* ctrl, int64_t cap, int64_t row_begin, int rpw, int nqb, int G,
+                 const int32_t* mask, const int32_t* qmask, int mw) {
   // LS_KNN_PRIO: 2 (default) MFMA clusters at raised priority, 1 half the waves raised, 0 none
   static const int prio = env_int("LS_KNN_PRIO", 2);
+  if constexpr (MM == 0) {
+    if (mask) {
+      knn_filter_q256_kernel<DD, 0, 8, 0, true><<<grid, 512, 0, stream>>>(X, N, Q, Qn, ws_s, ws_i, ctrl, cap, row_begin,
+                                                                         rpw, nqb, ws_s, G, prio, mask, qmask, mw);
+      return;
+    }
+  }
   // the timing-only ablations exist for the bench's shape (384 dims, main pass) only
   if constexpr (DD == 384 && MM == 1) {
     switch (abl) {
       case 1:
         knn_filter_q256_kernel<DD, MM, 8, 1><<<grid, 512, 0, stream>>>(X, N, Q, Qn, ws_s, ws_i, ctrl, cap, row_begin,
-                                                                       rpw, nqb, ws_s, G, prio);
+                                                                       rpw, nqb, ws_s, G, prio, nullptr, nullptr, 0);
         return;
       case 2:
         knn_filter_q256_kernel<DD, MM, 8, 2><<<grid, 512, 0, stream>>>(X, N, Q, Qn, ws_s, ws_i, ctrl, cap, row_begin,
-                                                                       rpw, nqb, ws_s, G, prio);
+                                                                       rpw, nqb, ws_s, G, prio, nullptr, nullptr, 0);
         return;
       case 3:
         knn_filter_q256_kernel<DD, MM, 8, 3><<<grid, 512, 0, stream>>>(X, N, Q, Qn, ws_s, ws_i, ctrl, cap, row_begin,
-                                                                       rpw, nqb, ws_s, G, prio);
+                                                                       rpw, nqb, ws_s, G, prio, nullptr, nullptr, 0);
         return;
       default:
         break;
     }
   }
   knn_filter_q256_kernel<DD, MM, 8><<<grid, 512, 0, stream>>>(X, N, Q, Qn, ws_s, ws_i, ctrl, cap, row_begin, rpw, nqb,
-                                                              ws_s, G, prio);
+                                                              ws_s, G, prio, nullptr, nullptr, 0);
 }
 
 __global__ void knn_init_kernel(int* __restrict__ ctrl, int Qn) {
@@ -831,7 +891,8 @@ __global__ void __launch_bounds__(256) knn_select4_kernel(const float* __restric
 // checks the overflow flags (ws_i tail) and reruns exactly if any is set.
 namespace {
 void knn_topk_impl(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::Tensor out_i, at::Tensor ws_s,
-                   at::Tensor ws_i, int64_t sample, int abl_req) {
+                   at::Tensor ws_i, int64_t sample, int abl_req, const int32_t* mask = nullptr,
+                   const int32_t* qmask = nullptr) {
   TORCH_CHECK(X.scalar_type() == at::kBFloat16 && Q.scalar_type() == at::kBFloat16);
   TORCH_CHECK(X.is_contiguous() && Q.is_contiguous() && X.dim() == 2 && Q.dim() == 2);
   const int dim = X.size(1);
@@ -849,6 +910,7 @@ void knn_topk_impl(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::
   TORCH_CHECK((int64_t)nchunks * nqg < (1LL << 31), "kNN grid too large");
   int* ctrl = ws_i.data_ptr<int32_t>() + (int64_t)Qn * nchunks * K;
   const int64_t cap = (int64_t)nchunks * K;
+  const int mw = 32 * nchunks;   // words per mask row
   knn_init_kernel<<<(Qn + 255) / 256, 256, 0, stream>>>(ctrl, Qn);
 #define DISPATCH_DIM(LAUNCH)                                       \
   switch (dim) {                                                   \
@@ -864,10 +926,15 @@ void knn_topk_impl(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::
   }
   auto exact = [&](int nc) {
     dim3 grid(nc * nqg);
-#define LAUNCH_E(DD)                                                                                          \
-  knn_exact_kernel<DD><<<grid, 256, 0, stream>>>((const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(),    \
-                                                 Qn, (int)K, ws_s.data_ptr<float>(), ws_i.data_ptr<int32_t>(), \
-                                                 ctrl, nchunks, 0, nc)
+#define LAUNCH_E(DD)                                                                                            \
+  if (mask)                                                                                                     \
+    knn_exact_kernel<DD, true><<<grid, 256, 0, stream>>>(                                                       \
+        (const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(), Qn, (int)K, ws_s.data_ptr<float>(),            \
+        ws_i.data_ptr<int32_t>(), ctrl, nchunks, 0, nc, mask, qmask);                                           \
+  else                                                                                                          \
+    knn_exact_kernel<DD><<<grid, 256, 0, stream>>>((const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(),    \
+                                                   Qn, (int)K, ws_s.data_ptr<float>(), ws_i.data_ptr<int32_t>(), \
+                                                   ctrl, nchunks, 0, nc, nullptr, nullptr)
     DISPATCH_DIM(LAUNCH_E)
 #undef LAUNCH_E
   };
@@ -891,7 +958,8 @@ void knn_topk_impl(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::
     dim3 grid(nrb * nqb);
 #define LAUNCH_Q(DD, MM)                                                                                         \
   launch_q256<DD, MM>(abl, grid, stream, (const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(), Qn,            \
-                      ws_s.data_ptr<float>(), ws_i.data_ptr<int32_t>(), ctrl, cap, row_begin, (int)rpw, nqb, G)
+                      ws_s.data_ptr<float>(), ws_i.data_ptr<int32_t>(), ctrl, cap, row_begin, (int)rpw, nqb, G,     \
+                      mask, qmask, mw)
 #define LAUNCH_QM(DD)                     \
   switch (mode) {                         \
     case 0: LAUNCH_Q(DD, 0); break;       \
@@ -917,10 +985,15 @@ void knn_topk_impl(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::
       return;
     }
     dim3 grid(nc * nqf);
-#define LAUNCH_F(DD)                                                                                            \
-  knn_filter_kernel<DD><<<grid, 256, 0, stream>>>((const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(), Qn, \
-                                                  ws_s.data_ptr<float>(), ws_i.data_ptr<int32_t>(), ctrl, cap, c0, \
-                                                  nc)
+#define LAUNCH_F(DD)                                                                                              \
+  if (mask)                                                                                                       \
+    knn_filter_kernel<DD, true><<<grid, 256, 0, stream>>>(                                                        \
+        (const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(), Qn, ws_s.data_ptr<float>(),                      \
+        ws_i.data_ptr<int32_t>(), ctrl, cap, c0, nc, mask, qmask, mw);                                            \
+  else                                                                                                            \
+    knn_filter_kernel<DD><<<grid, 256, 0, stream>>>((const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(), Qn, \
+                                                    ws_s.data_ptr<float>(), ws_i.data_ptr<int32_t>(), ctrl, cap,  \
+                                                    c0, nc, nullptr, nullptr, 0)
     DISPATCH_DIM(LAUNCH_F)
 #undef LAUNCH_F
   };
@@ -937,7 +1010,9 @@ void knn_topk_impl(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::
   const int64_t S = (int64_t)ns * CH;
   // LS_KNN_EXACT_SAMPLE is a presence test (set to anything, "0" included: the exact
   // sample), read per call -- hence the raw getenv
-  if (q256 && ns < nchunks && K <= 64 && N >= 2 * S && !getenv("LS_KNN_EXACT_SAMPLE")) {
+  // A masked search never takes this route: a group maximum over rows the mask rejects is
+  // no lower bound on the K-th best admitted score.  It takes the exact-sample route below.
+  if (q256 && !mask && ns < nchunks && K <= 64 && N >= 2 * S && !getenv("LS_KNN_EXACT_SAMPLE")) {
     const int nqb = (Qn + 255) / 256;
     const int64_t nrb_target = std::min<int64_t>(256, std::max<int64_t>(32, 256 / nqb));
     const int64_t rpw = std::max<int64_t>(64, ((S + nrb_target - 1) / nrb_target + 63) / 64 * 64);
@@ -964,6 +1039,22 @@ void knn_topk_impl(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::
 void knn_topk(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::Tensor out_i, at::Tensor ws_s,
               at::Tensor ws_i, int64_t sample) {
   knn_topk_impl(X, Q, K, out_s, out_i, ws_s, ws_i, sample, 0);
+}
+
+// Masked search (see knn_admitted): mask int32 [M, 32 * nchunks], qmask int32 [Qn] on the
+// device, values in [-1, M) -- the caller (ops.knn_topk) checks the values on the host
+// before the upload; the shapes are checked again here.
+void knn_topk_masked(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::Tensor out_i, at::Tensor ws_s,
+                     at::Tensor ws_i, int64_t sample, at::Tensor mask, at::Tensor qmask) {
+  TORCH_CHECK(X.dim() == 2 && Q.dim() == 2);
+  const int64_t nchunks = (X.size(0) + CH - 1) / CH;
+  TORCH_CHECK(mask.scalar_type() == at::kInt && qmask.scalar_type() == at::kInt, "kNN mask / qmask must be int32");
+  TORCH_CHECK(mask.is_contiguous() && qmask.is_contiguous() && mask.device() == X.device() &&
+              qmask.device() == X.device());
+  TORCH_CHECK(mask.dim() == 2 && mask.size(0) >= 1 && mask.size(1) == 32 * nchunks, "kNN mask must be [M, ",
+              32 * nchunks, "]");
+  TORCH_CHECK(qmask.dim() == 1 && qmask.size(0) == Q.size(0), "kNN qmask must be [Q]");
+  knn_topk_impl(X, Q, K, out_s, out_i, ws_s, ws_i, sample, 0, mask.data_ptr<int32_t>(), qmask.data_ptr<int32_t>());
 }
 
 // Timing-only ablations of the large-batch main pass (tools/engine_bench.py --knn-ablate):

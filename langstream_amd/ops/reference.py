@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 KV_BLOCK = 64
@@ -249,10 +250,28 @@ def pool_embeddings(x, start, length, mode, normalize):
     return o
 
 
-def knn_topk(X, Q, k):
+def knn_admitted(mask, qmask, Qn: int, N: int):
+    """bool [Qn, N]: the rows each query's mask admits.  mask: int32 [M, 32 * ceil(N / 1024)]
+    (bit b of word w = row 32w + b), qmask: [Qn] mask row per query, -1 = every row."""
+    qm = torch.as_tensor(qmask, dtype=torch.long).cpu()
+    words = mask.detach().cpu().numpy().astype(np.int32, copy=False)
+    bits = np.unpackbits(np.ascontiguousarray(words).view(np.uint8), axis=-1, bitorder="little")[:, :N]
+    bits = torch.from_numpy(bits.astype(bool)).reshape(words.shape[0], N)
+    adm = torch.ones(Qn, N, dtype=torch.bool)
+    sel = qm >= 0
+    if bool(sel.any()):
+        adm[sel] = bits[qm[sel]]
+    return adm
+
+
+def knn_topk(X, Q, k, mask=None, qmask=None):
     s = Q.float() @ X.float().t()
+    if mask is not None:
+        s = s.masked_fill(~knn_admitted(mask, qmask, Q.shape[0], X.shape[0]).to(s.device), float("-inf"))
     kk = min(k, X.shape[0])
     v, i = torch.topk(s, kk, dim=-1)
+    if mask is not None:
+        i = i.masked_fill(v == float("-inf"), -1)
     if kk < k:
         pad = k - kk
         v = torch.cat([v, v.new_full((v.shape[0], pad), float("-inf"))], -1)

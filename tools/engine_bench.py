@@ -102,21 +102,43 @@ def bench_embed(args):
                       "encoder_texts_per_s": round(512 / dt_f, 1)}), flush=True)
 
 
+def _time_ms(fn, iters=20, warm=3):
+    for _ in range(warm):
+        fn()
+    sync()
+    t0 = time.time()
+    for _ in range(iters):
+        fn()
+    sync()
+    return (time.time() - t0) / iters * 1000
+
+
 def bench_knn(args):
+    import numpy as np
+
     from langstream_amd import ops
+    from langstream_amd.engine.vector_store import pack_mask
     X = torch.nn.functional.normalize(torch.randn(args.rows, 384, device="cuda"), dim=-1).bfloat16()
+    fracs = [float(f) for f in str(args.knn_filter_frac).split(",") if f]
     for nq in str(args.queries).split(","):
         Q = torch.nn.functional.normalize(torch.randn(int(nq), 384, device="cuda"), dim=-1).bfloat16()
-        for _ in range(3):
-            ops.knn_topk(X, Q, 20, _ablate=args.knn_ablate)
-        sync()
-        t0 = time.time()
-        for _ in range(20):
-            ops.knn_topk(X, Q, 20, _ablate=args.knn_ablate)
-        sync()
-        dt = (time.time() - t0) / 20
-        print(json.dumps({"test": "knn", "rows": args.rows, "queries": int(nq), "ms": round(dt * 1000, 3),
-                          "GB_per_s": round(args.rows * 384 * 2 / dt / 1e9, 1)}), flush=True)
+        ms = _time_ms(lambda: ops.knn_topk(X, Q, 20, _ablate=args.knn_ablate))
+        print(json.dumps({"test": "knn", "rows": args.rows, "queries": int(nq), "ms": round(ms, 3),
+                          "GB_per_s": round(args.rows * 384 * 2 / ms / 1e6, 1)}), flush=True)
+        # --knn-filter-frac: the same queries restricted to a random subset of the rows (one
+        # mask for the batch), through the masked kernels and through the compact route
+        # (gather the admitted rows, search them unfiltered), next to the unfiltered time
+        for frac in fracs:
+            adm = np.random.default_rng(int(frac * 1e6)).random(args.rows) < frac
+            mask = torch.from_numpy(pack_mask(adm)[None]).cuda()
+            rows = torch.from_numpy(np.flatnonzero(adm)).cuda()
+            qmask = torch.zeros(int(nq), dtype=torch.int32)
+            ms_m = _time_ms(lambda: ops.knn_topk(X, Q, 20, mask=mask, qmask=qmask))
+            ms_c = _time_ms(lambda: ops.knn_topk(X.index_select(0, rows), Q, 20))
+            print(json.dumps({"test": "knn_filtered", "rows": args.rows, "queries": int(nq), "frac": frac,
+                              "admitted": int(rows.numel()), "masked_ms": round(ms_m, 3),
+                              "compact_ms": round(ms_c, 3), "unfiltered_ms": round(ms, 3),
+                              "masked_over_unfiltered": round(ms_m / ms, 3)}), flush=True)
 
 
 if __name__ == "__main__":
@@ -136,6 +158,9 @@ if __name__ == "__main__":
     ap.add_argument("--queries", default="64", help="comma-separated query counts (knn)")
     ap.add_argument("--knn-ablate", type=int, default=0,
                     help="kNN main-pass timing ablation 1-3 (diagnosis only: WRONG results)")
+    ap.add_argument("--knn-filter-frac", default="",
+                    help="comma-separated admitted fractions: also time the filtered search (masked kernels and "
+                         "compact route) next to the unfiltered one, e.g. 0.5,0.1")
     a = ap.parse_args()
     for w in a.what.split(","):
         {"llm": bench_llm, "embed": bench_embed, "knn": bench_knn}[w](a)
