@@ -54,7 +54,8 @@ class VectorCollectionManager(AssetManager):
     def deploy_asset(self) -> None:
         from ..engine.vector_store import VectorStoreRegistry
         dim = int(self.cfg.get("dimension") or self.cfg.get("dimensions") or 384)
-        VectorStoreRegistry.get(self.cfg["collection-name"], dim)
+        # similarity: cosine | dot-product | euclidean (None: cosine for a new collection)
+        VectorStoreRegistry.get(self.cfg["collection-name"], dim, metric=self.cfg.get("similarity") or None)
 
     def delete_asset_if_exists(self) -> None:
         from ..engine.vector_store import VectorStoreRegistry

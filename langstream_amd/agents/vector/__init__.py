@@ -16,7 +16,7 @@ from typing import Any, Dict, List
 
 from ...api.agent import AgentProcessor, AgentSink, completed, failed
 from ...api.record import SourceRecordAndResult
-from ...engine.vector_store import VectorStoreRegistry
+from ...engine.vector_store import VectorStoreRegistry, canonical_metric
 from ...engine.vector_store import _safe as _safe_name
 from ...runtime.registry import register_agent
 from ..genai.el import eval_expression
@@ -56,8 +56,9 @@ class _UpsertBatcher:
     A single flusher thread applies operations in submission order, so per-id order
     is kept; each record's future completes once its batch is applied (and logged)."""
 
-    def __init__(self, collection: str, max_batch: int = 512, linger_s: float = 0.002):
+    def __init__(self, collection: str, max_batch: int = 512, linger_s: float = 0.002, metric=None):
         self.collection = collection
+        self.metric = metric   # of the collection when an upsert creates it (None: cosine)
         self.max_batch = max_batch
         self.linger_s = linger_s
         self._q: List[tuple] = []
@@ -104,7 +105,7 @@ class _UpsertBatcher:
                     VectorStoreRegistry.get(self.collection).delete([it[1] for it in items])
             else:
                 dim = len(items[0][2])
-                VectorStoreRegistry.get(self.collection, dim).upsert(
+                VectorStoreRegistry.get(self.collection, dim, metric=self.metric).upsert(
                     [it[1] for it in items], [it[2] for it in items], [it[3] for it in items])
             for it in items:
                 it[4].set_result(None)
@@ -112,6 +113,22 @@ class _UpsertBatcher:
             for it in items:
                 if not it[4].done():
                     it[4].set_exception(e)
+
+
+def _local_sink_metric(cfg: Dict[str, Any]):
+    """The ``similarity`` of a local sink (its own key, else its datasource's; None: whatever
+    the collection has, cosine when the sink creates it).  A collection that exists, in
+    memory or persisted, with another metric is an error -- never a silent override."""
+    metric = cfg.get("similarity") or (cfg.get("datasource") or {}).get("similarity") or None
+    if metric is None:
+        return None
+    metric = canonical_metric(metric)
+    coll = cfg.get("collection-name") or (cfg.get("datasource") or {}).get("collection-name") or "default"
+    have = VectorStoreRegistry.metric_of(coll)
+    if have is not None and have != metric:
+        raise ValueError(f"vector-db-sink (local): collection {coll} has similarity {have}, "
+                         f"the sink is configured with {metric}")
+    return metric
 
 
 class _LocalWriter:
@@ -124,7 +141,8 @@ class _LocalWriter:
         names = {f.get("name") for f in self.fields}
         if "vector" not in names:
             raise ValueError("vector-db-sink (local): a field named 'vector' is required")
-        self.batcher = _UpsertBatcher(self.collection, int(cfg.get("batch-size", 512)))
+        self.metric = _local_sink_metric(cfg)
+        self.batcher = _UpsertBatcher(self.collection, int(cfg.get("batch-size", 512)), metric=self.metric)
 
     def upsert(self, mr: MutableRecord) -> Future:
         ctx = mr.el_context()
@@ -205,14 +223,15 @@ class _JdbcWriter:
                                  [], [vals[c] for c in allc])
 
     def _mirror_upsert(self, rowid, vals) -> None:
-        for (table, col), name in list(self.ds.vector_cols.items()):
+        # every mirror of the column: one per metric a query has used
+        for (table, col, _metric), name in list(self.ds.vector_cols.items()):
             if table == self.table.lower():
                 for k, v in vals.items():
                     if k.lower() == col and isinstance(v, list):
                         VectorStoreRegistry.get(name, len(v), persist=False).upsert([rowid], [v])
 
     def _mirror_delete(self, rowids) -> None:
-        for (table, col), name in list(self.ds.vector_cols.items()):
+        for (table, col, _metric), name in list(self.ds.vector_cols.items()):
             if table == self.table.lower() and VectorStoreRegistry.exists(name):
                 VectorStoreRegistry.get(name, persist=False).delete(rowids)
 
@@ -232,6 +251,7 @@ class VectorDBSinkAgent(AgentSink):
         if self._local:
             if ds.get("persist-directory"):
                 VectorStoreRegistry.configure(persist_dir=ds["persist-directory"], fsync=ds.get("fsync"))
+            _local_sink_metric(self.cfg)   # a metric clash fails the init
             self.writer = None   # built in set_context, once the durable default is known
         elif svc in ("jdbc", "sqlite"):
             self.writer = _JdbcWriter(self.cfg)

@@ -6,13 +6,17 @@ Parity: F6/F9 (AIA/.../datasource/*, VEC/*): QueryStepDataSource.fetchData(query
 MI355X-native services:
 * ``local`` / ``local-gpu``: HBM vector collections (engine/vector_store.py) with a JSON
   query language -- ``{"collection-name": "docs", "vector": ?, "top-k": 5,
-  "filter": {"field": ?}, "include-vector": false}`` (``?`` = positional params).
+  "filter": {"field": ?}, "include-vector": false}`` (``?`` = positional params).  The
+  collection's metric (``similarity: cosine | dot-product | euclidean`` where it is created)
+  decides the ranking; hits of a euclidean collection carry ``distance`` beside ``similarity``.
 * ``jdbc`` by URL (``JdbcDataSourceProvider.java:147-160`` picks the driver the same way):
   - ``jdbc:postgresql://...``: a real server through the in-tree v3 wire client
     (``pgwire.py``: SCRAM-SHA-256 / MD5 auth, prepared statements, typed results);
   - ``jdbc:sqlite:<path>`` (or ``service: sqlite``): SQLite (stdlib) with a
-    ``cosine_similarity`` UDF; the RAG pattern ``... ORDER BY cosine_similarity(<vector
-    col>, ?) DESC LIMIT k`` runs as a GPU kNN over an HBM mirror of the vector column
+    ``cosine_similarity`` / ``dot_product`` / ``euclidean_distance`` UDFs; the RAG pattern
+    ``... ORDER BY cosine_similarity(<vector col>, ?) DESC LIMIT k`` (likewise ``dot_product
+    ... DESC`` and ``euclidean_distance ... ASC``) runs as a GPU kNN over an HBM mirror of the
+    vector column, one mirror per metric
     (the reference example ``EX/docker-chatbot/chatbot.yaml:36`` runs that query on HerdDB);
   - ``jdbc:herddb:local`` (HerdDB's embedded, in-process mode) -> an in-process SQLite
     database shared by the process's agents;
@@ -35,7 +39,7 @@ import sqlite3
 import threading
 from typing import Any, Dict, List, Optional, Sequence
 
-from ...engine.vector_store import IdSet, VectorStoreRegistry
+from ...engine.vector_store import IdSet, VectorStoreRegistry, canonical_metric
 
 log = logging.getLogger(__name__)
 
@@ -131,9 +135,20 @@ class LocalVectorDataSource(DataSource):
         if cfg.get("persist-directory"):
             VectorStoreRegistry.configure(persist_dir=cfg["persist-directory"], fsync=cfg.get("fsync"))
         self.default_collection = cfg.get("collection-name") or cfg.get("collection") or "default"
+        # similarity: the metric of collections this datasource creates; an existing default
+        # collection with another metric is an error here, not a silent override
+        self.metric = canonical_metric(cfg["similarity"]) if cfg.get("similarity") else None
+        if self.metric is not None:
+            have = VectorStoreRegistry.metric_of(self.default_collection)
+            if have is not None and have != self.metric:
+                raise ValueError(f"vector collection {self.default_collection} has similarity {have}, the "
+                                 f"datasource is configured with {self.metric}")
 
     def _store(self, name: Optional[str], dim: Optional[int] = None):
-        return VectorStoreRegistry.get(name or self.default_collection, dim)
+        name = name or self.default_collection
+        # the configured metric applies to collections created here; an existing one keeps its own
+        metric = self.metric if dim is not None and VectorStoreRegistry.metric_of(name) is None else None
+        return VectorStoreRegistry.get(name, dim, metric=metric)
 
     def fetch_data(self, query, params):
         return self.fetch_data_batch(query, [params])[0]
@@ -196,10 +211,41 @@ def _cosine(a, b) -> Optional[float]:
     return num / (da * db) if da and db else 0.0
 
 
+def _vec(a):
+    return json.loads(a) if isinstance(a, str) else a
+
+
+def _dot(a, b) -> Optional[float]:
+    if a is None or b is None:
+        return None
+    return float(sum(x * y for x, y in zip(_vec(a), _vec(b))))
+
+
+def _euclid(a, b) -> Optional[float]:
+    if a is None or b is None:
+        return None
+    return math.sqrt(sum((x - y) * (x - y) for x, y in zip(_vec(a), _vec(b))))
+
+
+# ORDER BY <function>(col, ?) <direction> LIMIT k as a GPU kNN: each function with the one
+# direction that means "best first" (the other direction falls through to SQLite)
+_KNN_FUNCS = {"cosine_similarity": ("cosine", "desc"), "dot_product": ("dot-product", "desc"),
+              "euclidean_distance": ("euclidean", "asc")}
 _KNN = re.compile(
     r"^\s*select\s+(?P<cols>.+?)\s+from\s+(?P<table>[\w.]+)\s*(?P<where>where\s+.+?)?\s*order\s+by\s+"
-    r"cosine_similarity\s*\(\s*(?P<col>\w+)\s*,\s*(?:cast\s*\(\s*)?\?(?:\s+as\s+[\w\s]+\))?\s*\)\s+desc\s+"
+    r"(?P<fn>cosine_similarity|dot_product|euclidean_distance)\s*\(\s*(?P<col>\w+)\s*,\s*(?:cast\s*\(\s*)?\?"
+    r"(?:\s+as\s+[\w\s]+\))?\s*\)\s+(?P<dir>asc|desc)\s+"
     r"limit\s+(?P<k>\d+)\s*;?\s*$", re.I | re.S)
+
+
+def _knn_match(query: str):
+    """(match, metric) when the query is a kNN the GPU runs, else (None, None)."""
+    m = _KNN.match(query)
+    if m:
+        metric, direction = _KNN_FUNCS[m.group("fn").lower()]
+        if m.group("dir").lower() == direction:
+            return m, metric
+    return None, None
 
 _dbs: Dict[str, "SqliteDataSource"] = {}
 _dbs_lock = threading.Lock()
@@ -225,9 +271,13 @@ class SqliteDataSource(DataSource):
         else:
             self.conn = sqlite3.connect(self.path, check_same_thread=False)
         self.conn.create_function("cosine_similarity", 2, _cosine, deterministic=True)
+        self.conn.create_function("dot_product", 2, _dot, deterministic=True)
+        self.conn.create_function("euclidean_distance", 2, _euclid, deterministic=True)
         self.conn.row_factory = sqlite3.Row
         self.lock = lock if lock is not None else threading.RLock()
-        self.vector_cols: Dict[tuple, str] = {}  # (table, column) -> store name
+        # (table, column, metric) -> store name: a cosine mirror holds normalised rows, so
+        # every metric a query has used on a column has a mirror of its own
+        self.vector_cols: Dict[tuple, str] = {}
 
     @staticmethod
     def shared(cfg: Dict[str, Any]) -> "SqliteDataSource":
@@ -239,8 +289,9 @@ class SqliteDataSource(DataSource):
                 _dbs[key] = ds
             return ds
 
-    def _store_name(self, table: str, col: str) -> str:
-        return f"sqlite:{self.name}:{table.lower()}:{col.lower()}"
+    def _store_name(self, table: str, col: str, metric: str = "cosine") -> str:
+        base = f"sqlite:{self.name}:{table.lower()}:{col.lower()}"
+        return base if metric == "cosine" else f"{base}:{metric}"
 
     def _sql_param(self, p):
         if isinstance(p, (list, dict)):
@@ -248,14 +299,14 @@ class SqliteDataSource(DataSource):
         return p
 
     def fetch_data(self, query, params):
-        m = _KNN.match(query)
+        m, metric = _knn_match(query)
         if m:
             table, col, k = m.group("table"), m.group("col"), int(m.group("k"))
-            name = self._store_name(table, col)
+            name = self._store_name(table, col, metric)
             vec = params[-1]
             if isinstance(vec, str):
                 vec = json.loads(vec)
-            self._ensure_mirror(table, col, len(vec))
+            self._ensure_mirror(table, col, len(vec), metric)
             store = VectorStoreRegistry.get(name, persist=False)
             flt = None
             if m.group("where"):
@@ -290,12 +341,12 @@ class SqliteDataSource(DataSource):
             return res
 
     # --- HBM mirror of vector columns
-    def _ensure_mirror(self, table: str, col: str, dim: int) -> None:
-        key = (table.lower(), col.lower())
+    def _ensure_mirror(self, table: str, col: str, dim: int, metric: str = "cosine") -> None:
+        key = (table.lower(), col.lower(), metric)
         if key in self.vector_cols:
             return
-        name = self._store_name(table, col)
-        store = VectorStoreRegistry.get(name, dim, persist=False)  # a mirror: rebuilt from SQL
+        name = self._store_name(table, col, metric)
+        store = VectorStoreRegistry.get(name, dim, persist=False, metric=metric)  # a mirror: rebuilt from SQL
         with self.lock:
             rows = self.conn.execute(f"SELECT rowid, {col} FROM {table}").fetchall()
         ids, vecs = [], []
@@ -327,10 +378,10 @@ class SqliteDataSource(DataSource):
 
     def _invalidate_mirrors_for(self, query: str) -> None:
         ql = query.lower()
-        for (table, col), name in list(self.vector_cols.items()):
+        for (table, col, metric), name in list(self.vector_cols.items()):   # every metric's mirror
             if re.search(rf"\b{re.escape(table)}\b", ql):
                 VectorStoreRegistry.drop(name)
-                self.vector_cols.pop((table, col), None)
+                self.vector_cols.pop((table, col, metric), None)
 
 
 def _decode_row(r: Dict[str, Any]) -> Dict[str, Any]:

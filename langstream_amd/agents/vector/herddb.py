@@ -27,7 +27,7 @@ import re
 import threading
 from typing import Any, Dict, Optional, Tuple
 
-from .datasources import SqliteDataSource, _cosine
+from .datasources import SqliteDataSource, _cosine, _dot, _euclid
 from .pg_standalone import PgStandalone
 
 DEFAULT_PORT = 7000
@@ -85,7 +85,8 @@ class HerdDBServer:
         self.lock = threading.RLock()
         self._ds: Optional[SqliteDataSource] = None
         self.pg = PgStandalone(host, port, users=dict(users or DEFAULT_USERS), auth="scram-sha-256",
-                               db_uri=self.uri, functions={"cosine_similarity": (2, _cosine)},
+                               db_uri=self.uri, functions={"cosine_similarity": (2, _cosine), "dot_product": (2, _dot),
+                                                            "euclidean_distance": (2, _euclid)},
                                rewrite=herddb_sql, on_write=self._on_write, db_lock=self.lock,
                                server_version="16.0 (langstream herddb service)")
         self.host, self.port = self.pg.host, self.pg.port

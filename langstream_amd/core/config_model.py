@@ -38,6 +38,7 @@ class Prop:
     items: Optional["Prop"] = None
     properties: Optional[Dict[str, "Prop"]] = None
     el: bool = False                            # value is an EL expression (or a list of them)
+    choices: Optional[List[str]] = None         # string: the values it may take
 
     def doc(self) -> Dict[str, Any]:
         d: Dict[str, Any] = {"description": self.description, "required": self.required, "type": self.type}
@@ -64,8 +65,12 @@ class Model:
                 "properties": {k: v.doc() for k, v in self.properties.items()}}
 
 
-def S(desc="", required=False, default=None, el=False):
-    return Prop("string", desc, required, default, el=el)
+def S(desc="", required=False, default=None, el=False, choices=None):
+    return Prop("string", desc, required, default, el=el, choices=choices)
+
+
+# the metrics of a local vector collection (engine/vector_store.py METRICS and their spellings)
+_SIMILARITY = ["cosine", "dot-product", "euclidean", "dot", "dot_product", "l2"]
 
 
 def I(desc="", required=False, default=None):
@@ -274,6 +279,9 @@ _SINK_FIELDS = L("Fields to write.", True, _NAMED_EXPR)
 VECTOR_SINK_MODELS: Dict[str, Model] = {
     "local": Model("Local GPU vector store", "Writes into the HBM-resident vector collection.", {
         "collection-name": S("Collection."), "fields": L("Fields to write.", items=_NAMED_EXPR),
+        "similarity": S("Similarity metric of the collection when the sink creates it: cosine (default), "
+                        "dot-product or euclidean; an existing collection with another metric is an error.",
+                        choices=_SIMILARITY),
         "batch-size": I("Max records per batched store mutation.", default=512)}),
     "jdbc": Model("JDBC", "Upserts rows into a table.", {
         "table-name": S("Table.", True), "fields": L("Columns.", True, O(properties={
@@ -362,7 +370,10 @@ DATASOURCE_MODELS: Dict[str, Model] = {
     "local": Model("Local GPU vector store", "HBM-resident vector collections + SQLite tables.", {
         "path": S("SQLite path."), "persist-directory": S("Vector-store persistence directory (WAL + snapshots)."),
         "fsync": B("fsync every WAL append (default: flush to the OS only)."), "collection": S("Default collection."),
-        "collection-name": S("Default collection."), "url": S("SQLite URL.")}, allow_unknown=True),
+        "collection-name": S("Default collection."), "url": S("SQLite URL."),
+        "similarity": S("Similarity metric of the collections this datasource creates: cosine (default), "
+                        "dot-product or euclidean; an existing default collection with another metric is an "
+                        "error.", choices=_SIMILARITY)}, allow_unknown=True),
 }
 for _a, _b in (("local-gpu", "local"), ("sqlite", "jdbc")):
     DATASOURCE_MODELS[_a] = DATASOURCE_MODELS[_b]
@@ -396,7 +407,9 @@ ASSET_MODELS: Dict[str, Model] = {
         "vector-dimension": I("Vector dimension.", True)}),
     "vector-collection": Model("GPU vector collection", "An HBM-resident vector collection.", {
         "datasource": S("Datasource."), "collection-name": S("Collection.", True),
-        "dimension": I("Vector dimension."), "dimensions": I("Vector dimension (alias).")}, allow_unknown=True),
+        "dimension": I("Vector dimension."), "dimensions": I("Vector dimension (alias)."),
+        "similarity": S("Similarity metric: cosine (default), dot-product or euclidean.", choices=_SIMILARITY)},
+        allow_unknown=True),
 }
 
 
@@ -416,6 +429,8 @@ def _convert(p: Prop, v: Any, ref: str, key: str) -> Any:
     if p.type == "string":
         if isinstance(v, (dict, list)):
             raise bad
+        if p.choices is not None and str(v).strip().lower() not in p.choices:
+            raise _err(ref, key, f"must be one of {p.choices[:3]}, got '{v}'")
         return v
     if p.type == "integer":
         if isinstance(v, bool):

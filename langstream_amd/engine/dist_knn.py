@@ -44,7 +44,7 @@ import torch
 import torch.distributed as dist
 
 from ..utils.gpu import on_search, to_host
-from .vector_store import VectorStoreRegistry, canonical_filter
+from .vector_store import VectorStoreRegistry, canonical_filter, euclidean_fields
 
 log = logging.getLogger(__name__)
 
@@ -71,10 +71,11 @@ def stop() -> None:
 
 
 class _Req:
-    __slots__ = ("coll", "q", "k", "inc", "flt", "fut")
+    __slots__ = ("coll", "q", "k", "inc", "flt", "fut", "metric", "qn2")
 
-    def __init__(self, coll, q, k, inc, flt=None):
+    def __init__(self, coll, q, k, inc, flt=None, metric="cosine", qn2=None):
         self.coll, self.q, self.k, self.inc, self.flt = coll, q, k, inc, flt
+        self.metric, self.qn2 = metric, qn2   # qn2: euclidean, |q|^2 of the rounded queries
         self.fut: Future = Future()
 
 
@@ -122,12 +123,23 @@ class ShardedKnn:
     # ------------------------------------------------------------------ client API
     def search(self, collection: str, queries, k: int, with_vectors: bool = False, filter=None) -> Future:
         """Global top-k for the rows of ``queries`` ([Q, d]) -> Future[List[List[dict]]]
-        in the local store's result format (id, similarity, metadata[, vector]).
+        in the local store's result format (id, similarity, metadata[, vector]; ``distance``
+        too for a euclidean collection).  The collection's metric (``VectorStoreRegistry.
+        metric_of``, cosine when this rank does not know the collection) decides how the
+        queries are prepared and travels in the round header; the shards answer with the
+        kernel score, higher is better for every metric, so the merge is the same.
         ``filter``: as ``VectorStore.search`` -- one filter for all queries or one (or None)
         per query; it is checked here, so a malformed filter fails only its own request."""
         q = np.array(queries.cpu() if isinstance(queries, torch.Tensor) else queries, dtype=np.float32, ndmin=2)
-        q = q / np.maximum(np.linalg.norm(q, axis=-1, keepdims=True), 1e-12)
-        r = _Req(collection, q, int(k), bool(with_vectors))
+        metric = VectorStoreRegistry.metric_of(collection) or "cosine"
+        qn2 = None
+        if metric == "cosine":
+            q = q / np.maximum(np.linalg.norm(q, axis=-1, keepdims=True), 1e-12)
+        elif metric == "euclidean":
+            # |q|^2 of THIS rank's queries as the kernels see them, for score -> distance
+            st = VectorStoreRegistry._stores.get(collection)
+            qn2 = torch.from_numpy(q).to(st.dtype if st is not None else torch.bfloat16).float().pow(2).sum(-1).tolist()
+        r = _Req(collection, q, int(k), bool(with_vectors), metric=metric, qn2=qn2)
         try:
             per_q = filter if isinstance(filter, (list, tuple)) else [filter] * q.shape[0]
             if len(per_q) != q.shape[0]:
@@ -242,7 +254,8 @@ class ShardedKnn:
                         n += r.q.shape[0]
                     stopping = self._stop and not take and not self._pending
                 hdr = {"s": stopping,
-                       "r": [[r.coll, int(r.q.shape[0]), r.k, r.inc, int(r.q.shape[1]), r.flt] for r in take]}
+                       "r": [[r.coll, int(r.q.shape[0]), r.k, r.inc, int(r.q.shape[1]), r.flt, r.metric]
+                             for r in take]}
                 t_h = time.perf_counter()
                 hdrs = [json.loads(b) for b in self._allgather_bytes(json.dumps(hdr).encode())]
                 dt_h = time.perf_counter() - t_h
@@ -344,6 +357,12 @@ class ShardedKnn:
                 s = idx = None
                 if store is not None and store.dim == dim and len(store):
                     try:
+                        metrics = {r[6] if len(r) > 6 else "cosine" for _, r in reqs_all}
+                        if metrics != {store.metric}:
+                            # the queries were prepared for another metric than this shard's:
+                            # contribute nothing, keep the collectives in step
+                            raise ValueError(f"collection {coll}: shard {me} has metric {store.metric}, "
+                                             f"the round's queries {sorted(metrics)}")
                         # LS_KNN_REPLICATE=R (diagnosis): search the gathered queries R times
                         # over, i.e. the per-round load of R x W ranks, and keep the first copy
                         qs = qall if self._replicate <= 1 else qall.repeat(self._replicate, 1)
@@ -473,14 +492,17 @@ class ShardedKnn:
                 r.fut.set_exception(errs[r.coll])
                 continue
             out = []
-            for lst in hits.get(id(r), [[] for _ in range(r.q.shape[0])]):
+            for qj, lst in enumerate(hits.get(id(r), [[] for _ in range(r.q.shape[0])])):
                 res = []
                 for sc, o, rw in lst:
                     p = payload[o].get(r.coll, {}).get(rw)
                     if p is None:
                         continue
                     d = dict(p[0])
-                    d["similarity"] = sc
+                    if r.qn2 is None:
+                        d["similarity"] = sc
+                    else:   # euclidean: |q|^2 of the requesting rank's own query
+                        d["similarity"], d["distance"] = euclidean_fields(sc, r.qn2[qj])
                     if r.inc and p[1] is not None:
                         v = p[1]
                         d["vector"] = (v if isinstance(v, np.ndarray) else np.frombuffer(v, np.float32)).tolist()

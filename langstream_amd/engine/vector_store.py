@@ -1,6 +1,7 @@
 """HBM-resident vector store with brute-force kNN on the GPU.
 
-Rows are L2-normalised bf16 vectors in one device tensor ``[capacity, dim]`` (dense:
+Rows are bf16 vectors (L2-normalised for the default ``cosine`` metric, as given for
+``dot-product`` and ``euclidean``: see ``METRICS``) in one device tensor ``[capacity, dim]`` (dense:
 deletes move tail rows into the holes, so ``[0, n)`` is always valid and the kNN kernel
 never scans dead rows).  Search is the fused MFMA GEMM + top-k kernel
 (``ops.knn_topk``), so cosine similarity over 10^6-10^7 rows per GPU is one kernel pass
@@ -54,6 +55,34 @@ COMPACT_MAX = int(os.environ.get("LS_KNN_COMPACT_MAX", 262144))
 # for any mix: a batch with more distinct selective filters than this stays masked.
 COMPACT_FILTERS = 4
 MASK_CACHE_SIZE = 16
+
+# Similarity metric of a collection.  The kNN kernels rank by one "higher is better" score,
+# dot(q, x) + bias[x]:
+#   cosine       rows and queries are L2-normalised, no bias: the score is the cosine;
+#   dot-product  rows and queries as given (rounded to the store dtype), no bias;
+#   euclidean    rows and queries as given, bias[x] = -|x|^2 / 2 (an f32 device buffer beside
+#                the rows, never persisted): |q - x|^2 = |q|^2 - 2 * score, so the largest
+#                score is the smallest distance.
+METRICS = ("cosine", "dot-product", "euclidean")
+_METRIC_SPELLINGS = {"dot": "dot-product", "dot_product": "dot-product", "l2": "euclidean"}
+
+
+def canonical_metric(metric) -> str:
+    """The canonical name of a metric spelling; ValueError for anything else."""
+    m = str(metric).strip().lower() if metric is not None else ""
+    m = _METRIC_SPELLINGS.get(m, m)
+    if m not in METRICS:
+        raise ValueError(f"unknown similarity metric {metric!r}: one of {', '.join(METRICS)}")
+    return m
+
+
+def euclidean_fields(score: float, q_norm2: float) -> Tuple[float, float]:
+    """(similarity, distance) of a euclidean hit from its kernel score and |q|^2 of the rounded
+    query: d^2 = max(0, |q|^2 - 2 * score), similarity = 1 / (1 + d^2) (Cassandra's
+    ``similarity_euclidean``), distance = sqrt(d^2).  d^2 is a difference of f32 sums of the
+    stored (rounded) values: when it is small against |x|^2 it keeps few digits."""
+    d2 = max(0.0, q_norm2 - 2.0 * score)
+    return 1.0 / (1.0 + d2), d2 ** 0.5
 
 _FIELD_OPS = ("$eq", "$ne", "$in", "$nin")
 
@@ -174,6 +203,31 @@ class _Persistence:
         self.old_vec = os.path.join(directory, "snapshot.vec")
         self._wal = None
 
+    @classmethod
+    def read_metric(cls, directory: str) -> Optional[str]:
+        """The metric the directory records: the snapshot header's ``metric`` key, else the
+        ``collection.json`` sidecar (written when the collection is first opened, so before
+        its first acknowledged upsert); None for a directory written before metrics existed
+        (a cosine collection) or one that does not exist."""
+        hdr = cls.read_snapshot_header(os.path.join(directory, "snapshot.lsv"))
+        if hdr is not None and hdr[0].get("metric"):
+            return str(hdr[0]["metric"])
+        side = os.path.join(directory, "collection.json")
+        if os.path.exists(side):
+            with open(side) as f:
+                m = json.load(f).get("metric")
+            return str(m) if m else None
+        return None
+
+    def write_metric(self, metric: str) -> None:
+        side = os.path.join(self.dir, "collection.json")
+        tmp = side + ".tmp"
+        with open(tmp, "w") as f:
+            json.dump({"metric": metric}, f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, side)
+
     def _open_wal(self) -> None:
         if self._wal is None:
             self._wal = open(self.wal_path, "ab")
@@ -267,11 +321,11 @@ class _Persistence:
                 os.fsync(f.fileno())
         return dim, ids, metas, vec, entries
 
-    def snapshot(self, dim: int, ids, metas, vec: torch.Tensor) -> None:
+    def snapshot(self, dim: int, ids, metas, vec: torch.Tensor, metric: str = "cosine") -> None:
         tmp = self.snap_path + ".tmp"
         bf16 = vec.dtype == torch.bfloat16
-        hdr = json.dumps({"dim": dim, "dtype": "bfloat16" if bf16 else "float32", "ids": list(ids),
-                          "meta": list(metas)}).encode()
+        hdr = json.dumps({"dim": dim, "dtype": "bfloat16" if bf16 else "float32", "metric": metric,
+                          "ids": list(ids), "meta": list(metas)}).encode()
         with open(tmp, "wb") as f:
             f.write(self.MAGIC + len(hdr).to_bytes(8, "little") + hdr)
             (vec.view(torch.int16) if bf16 else vec.float()).numpy().tofile(f)
@@ -307,9 +361,14 @@ SEARCH_RETRIES = 3   # lock-free top-k attempts a renumbering delete may invalid
 
 class VectorStore:
     def __init__(self, dim: int, device="cuda", capacity: int = 1024, dtype=torch.bfloat16, name: str = "default",
-                 persist_dir: Optional[str] = None, fsync: bool = False):
+                 persist_dir: Optional[str] = None, fsync: bool = False, metric: Optional[str] = "cosine"):
+        """``metric``: ``cosine`` (default), ``dot-product`` or ``euclidean`` (``METRICS``; also
+        ``dot``, ``dot_product``, ``l2``); None takes what ``persist_dir`` records, else cosine.
+        A persisted collection opened with another metric than its own raises ValueError."""
         self.dim = dim
         self.name = name
+        self._metric_given = metric is not None
+        self.metric = canonical_metric(metric) if metric is not None else "cosine"
         self.device = torch.device(device)
         self.dtype = dtype
         self.kernel_dim = dim in KERNEL_DIMS
@@ -318,6 +377,7 @@ class VectorStore:
                         "GEMM + torch.topk path", name, dim, KERNEL_DIMS)
         with on_search(self.device):  # every GPU op of the store runs on the search stream
             self._vecs = torch.zeros(max(16, capacity), dim, device=self.device, dtype=dtype)
+        self._bias: Optional[torch.Tensor] = None   # euclidean: f32 [capacity], -|row|^2 / 2
         self._n = 0
         self._ids: List[Any] = []
         self._meta: List[Dict[str, Any]] = []
@@ -333,6 +393,9 @@ class VectorStore:
         self.filter_stats = {"compact": 0, "masked": 0, "mask_builds": 0}
         self.search_retries = 0
         self._persist = _Persistence(persist_dir, fsync) if persist_dir else None
+        if self._persist is not None:
+            self._adopt_metric()
+        self._init_bias()
         if self._persist is not None:
             with on_search(self.device), self.lock:
                 self._restore()
@@ -355,9 +418,36 @@ class VectorStore:
             if self._n:
                 return False
             self._persist = _Persistence(persist_dir, fsync)
+            try:
+                self._metric_given = True   # the store has served with its metric already
+                self._adopt_metric()
+            except ValueError:
+                self._persist = None
+                raise
             self._restore()
             self._mark_written()
             return True
+
+    def _adopt_metric(self) -> None:
+        """Reconcile the store's metric with the one its directory records, and record it when
+        the directory has none yet (before any upsert is acknowledged)."""
+        on_disk = _Persistence.read_metric(self._persist.dir)
+        held = os.path.exists(self._persist.snap_path) or os.path.exists(self._persist.old_meta) or (
+            os.path.exists(self._persist.wal_path) and os.path.getsize(self._persist.wal_path) > 4)
+        if on_disk is None and held:
+            on_disk = "cosine"   # written before collections had a metric
+        if on_disk is not None:
+            on_disk = canonical_metric(on_disk)
+            if self._metric_given and on_disk != self.metric:
+                raise ValueError(f"persisted collection {self.name} has metric {on_disk}, opened with {self.metric}")
+            self.metric = on_disk
+        if _Persistence.read_metric(self._persist.dir) is None:
+            self._persist.write_metric(self.metric)
+
+    def _init_bias(self) -> None:
+        if self.metric == "euclidean" and self._bias is None:
+            with on_search(self.device):
+                self._bias = torch.zeros(self._vecs.shape[0], device=self.device, dtype=torch.float32)
 
     # ------------------------------------------------------------------ mutation
     def _grow(self, need: int) -> None:
@@ -369,6 +459,10 @@ class VectorStore:
         nv = torch.zeros(cap, self.dim, device=self.device, dtype=self.dtype)
         nv[: self._n] = self._vecs[: self._n]
         self._vecs = nv
+        if self._bias is not None:
+            nb = torch.zeros(cap, device=self.device, dtype=torch.float32)
+            nb[: self._n] = self._bias[: self._n]
+            self._bias = nb
 
     def _normalize(self, v) -> torch.Tensor:
         t = torch.as_tensor(v, dtype=torch.float32)
@@ -378,6 +472,18 @@ class VectorStore:
             raise ValueError(f"vector dim {t.shape[-1]} != collection {self.name} dim {self.dim}")
         t = t.to(self.device)
         return torch.nn.functional.normalize(t, dim=-1, eps=1e-12).to(self.dtype)
+
+    def _prepare(self, v) -> torch.Tensor:
+        """Device vectors as the collection stores them: normalised for cosine, as given for
+        the other metrics, rounded to the store dtype."""
+        if self.metric == "cosine":
+            return self._normalize(v)
+        t = torch.as_tensor(v, dtype=torch.float32)
+        if t.dim() == 1:
+            t = t[None]
+        if t.shape[-1] != self.dim:
+            raise ValueError(f"vector dim {t.shape[-1]} != collection {self.name} dim {self.dim}")
+        return t.to(self.device).to(self.dtype)
 
     def upsert(self, ids: Sequence[Any], vectors, metadata: Optional[Sequence[Dict[str, Any]]] = None) -> None:
         metadata = list(metadata) if metadata is not None else [{} for _ in ids]
@@ -389,7 +495,7 @@ class VectorStore:
         with on_search(self.device), self.lock:
             # device vectors come from the embedding engine's auxiliary stream
             torch.cuda.current_stream().wait_stream(aux_stream(self.device))
-            vecs = self._normalize(vectors)
+            vecs = self._prepare(vectors)
             if vecs.shape[0] != len(ids):
                 raise ValueError("ids and vectors lengths differ")
             if self._persist is not None:
@@ -404,7 +510,7 @@ class VectorStore:
         the lock covers only the WAL append and the device scatter -- a search waits for
         a few calls instead of the whole upsert (every torch call is a GIL hand-off, and
         on a busy process each hand-off can wait behind other threads)."""
-        host = self._normalize_host(vectors)
+        host = self._prepare_host(vectors)
         if host.shape[0] != len(ids):
             raise ValueError("ids and vectors lengths differ")
         t = torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32)).to(self.dtype)
@@ -446,8 +552,11 @@ class VectorStore:
             last[r] = j
         src = list(last.values())
         dst = torch.tensor(list(last.keys()), device=self.device, dtype=torch.long)
-        self._vecs.index_copy_(0, dst, vecs[torch.tensor(src, device=self.device, dtype=torch.long)]
-                               if len(src) != len(rows) else vecs)
+        if len(src) != len(rows):
+            vecs = vecs[torch.tensor(src, device=self.device, dtype=torch.long)]
+        self._vecs.index_copy_(0, dst, vecs)
+        if self._bias is not None:   # from the stored (rounded) rows, in fp32
+            self._bias.index_copy_(0, dst, vecs.float().pow(2).sum(-1).mul_(-0.5))
 
     def delete(self, ids: Sequence[Any]) -> int:
         with on_search(self.device), self.lock:
@@ -474,6 +583,8 @@ class VectorStore:
             src = torch.tensor(fillers, device=self.device, dtype=torch.long)
             dst = torch.tensor(holes, device=self.device, dtype=torch.long)
             self._vecs.index_copy_(0, dst, self._vecs.index_select(0, src))
+            if self._bias is not None:
+                self._bias.index_copy_(0, dst, self._bias.index_select(0, src))
             for h, f in zip(holes, fillers):
                 self._ids[h] = self._ids[f]
                 self._meta[h] = self._meta[f]
@@ -495,7 +606,7 @@ class VectorStore:
         for e in entries:
             if e[0] == "u":
                 vf = np.frombuffer(e[2], dtype=np.float32).reshape(len(e[1]), self.dim).copy()
-                self._apply_upsert(e[1], self._normalize(vf), e[3])
+                self._apply_upsert(e[1], self._prepare(vf), e[3])
             elif e[0] == "d":
                 present = [k for k in e[1] if k in self._row]
                 if present:
@@ -531,7 +642,7 @@ class VectorStore:
             return
         with on_search(self.device), self.lock:
             v = to_host(self._vecs[: self._n].contiguous())[0]
-            self._persist.snapshot(self.dim, self._ids, self._meta, v)
+            self._persist.snapshot(self.dim, self._ids, self._meta, v, self.metric)
 
     def close(self) -> None:
         if self._persist is not None:
@@ -544,6 +655,7 @@ class VectorStore:
             return None if r is None else dict(self._meta[r])
 
     def vector(self, key: Any) -> Optional[List[float]]:
+        """The stored row: normalised for cosine, the rounded input for the other metrics."""
         with self.lock:
             r = self._row.get(key)
             if r is None:
@@ -711,10 +823,11 @@ class VectorStore:
             self.filter_stats["compact"] += 1
             sel = torch.tensor([i for i, w in enumerate(which) if w == j], device=self.device)
             Xc = self._vecs.index_select(0, rows)
+            bc = self._bias.index_select(0, rows) if self._bias is not None else None
             if self.device.type == "cuda" and self.kernel_dim and k <= KERNEL_MAX_K:
-                s, i = ops.knn_topk(Xc, q[sel].contiguous(), k)
+                s, i = ops.knn_topk(Xc, q[sel].contiguous(), k, bias=bc)
             else:
-                s, i = _exact_topk(Xc, q[sel], k)
+                s, i = _exact_topk(Xc, q[sel], k, bias=bc)
             # compact indices ascend with the row numbers, so ties still go to the lower row
             out_s[sel] = s
             out_i[sel] = torch.where(i >= 0, rows[i.clamp_min(0).long()].int(), i)
@@ -724,8 +837,10 @@ class VectorStore:
     def topk_rows(self, q: torch.Tensor, k: int, mask: Optional[torch.Tensor] = None,
                   qmask=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Device top-k over the live rows (caller holds ``lock``; any stream -- the read
-        is ordered after the store's last write).  q: normalised [Q, dim] in the store dtype.  Returns (scores f32 [Q,k],
-        rows int32 [Q,k]); missing entries are (-inf, -1).  ``mask`` (device int32
+        is ordered after the store's last write).  q: prepared queries (``_prepare_host``: normalised for cosine)
+        [Q, dim] in the store dtype.  Returns (scores f32 [Q,k], rows int32 [Q,k]); missing
+        entries are (-inf, -1).  The score is the kernel's, higher is better for every metric:
+        the cosine, the dot product, or for euclidean ``q.x - |x|^2 / 2``.  ``mask`` (device int32
         [M, 32 * ceil(n / 1024)], ``pack_mask`` rows) and ``qmask`` (host list / tensor [Q]:
         mask row per query, -1 = none) restrict each query to the rows its mask admits."""
         n = self._n
@@ -735,9 +850,10 @@ class VectorStore:
                     torch.full((Qn, k), -1, device=self.device, dtype=torch.int32))
         self._order_read()
         X = self._vecs[:n]
+        bias = self._bias[:n] if self._bias is not None else None
         if self.device.type == "cuda" and self.kernel_dim and k <= KERNEL_MAX_K:
-            return ops.knn_topk(X, q.contiguous(), k, mask=mask, qmask=qmask)
-        return _exact_topk(X, q, k, mask=mask, qmask=qmask)
+            return ops.knn_topk(X, q.contiguous(), k, mask=mask, qmask=qmask, bias=bias)
+        return _exact_topk(X, q, k, mask=mask, qmask=qmask, bias=bias)
 
     def _query_filters(self, filter, Qn: int) -> Optional[List[Any]]:
         """``search``'s filter argument as one entry per query (None: no query is filtered)."""
@@ -753,7 +869,11 @@ class VectorStore:
 
     def search(self, queries, k: int = 10, with_vectors: bool = False, filter=None) -> List[List[Dict[str, Any]]]:
         """queries: [Q, dim] (list or tensor).  Returns per query a list of
-        {"id", "similarity", **metadata} sorted by decreasing cosine similarity.
+        {"id", "similarity", **metadata} sorted best first; ``similarity`` is "higher is
+        better" for every metric: the cosine, the dot product, or for a euclidean collection
+        ``1 / (1 + d^2)`` beside ``distance`` = d (``euclidean_fields``).  Distances are those
+        of the stored bf16 values (rows and query rounded to the store dtype), and d^2 loses
+        digits when it is small against |x|^2.
         ``filter``: one filter for all queries or a list with one filter or None per query
         (grammar: ``check_filter``); each query gets the exact top-k of the rows it admits."""
         if k < 1:
@@ -764,7 +884,7 @@ class VectorStore:
         # pinned H2D copy on the search stream (the sharded service's path, which measured
         # 26 ms per round in the RAG bench where this one took 30-170 ms per batch:
         # profiles/r5/bench_stage_trace_r5j.log vs knn_w8load_r5o.log)
-        qn = self._normalize_host(queries)
+        qn = self._prepare_host(queries)
         filters = self._query_filters(filter, qn.shape[0])
         topk = self.topk_rows if filters is None else (lambda q_, k_: self.topk_filtered(q_, k_, filters))
         # The lock is held while work is ENQUEUED, not while the GPU runs it: the top-k and
@@ -815,7 +935,7 @@ class VectorStore:
                     ev.synchronize()
                 vec_rows = (flat, outs[0].numpy() if flat else np.zeros((0, self.dim), np.float32))
         # the result objects are built after the lock is released
-        out = self._build_results(hits, vec_rows)
+        out = self._build_results(hits, vec_rows, self.query_norm2(qn))
         if tr is not None:
             tr.append((t_in, t_lk, t_gpu, time.time(), len(out)))
         return out
@@ -831,6 +951,28 @@ class VectorStore:
             raise ValueError(f"vector dim {a.shape[-1]} != collection {self.name} dim {self.dim}")
         return a / np.maximum(np.linalg.norm(a, axis=-1, keepdims=True), 1e-12)
 
+    def _prepare_host(self, v) -> np.ndarray:
+        """Host queries / rows as float32 [n, dim]: normalised for cosine, as given otherwise."""
+        if self.metric == "cosine":
+            return self._normalize_host(v)
+        if isinstance(v, torch.Tensor):
+            a = v.detach().float().cpu().numpy()
+        else:
+            a = np.asarray(v, dtype=np.float32)
+        if a.ndim == 1:
+            a = a[None]
+        if a.shape[-1] != self.dim:
+            raise ValueError(f"vector dim {a.shape[-1]} != collection {self.name} dim {self.dim}")
+        return a
+
+    def query_norm2(self, a: np.ndarray) -> Optional[List[float]]:
+        """euclidean: |q|^2 of each prepared query as the kernels see it (rounded to the store
+        dtype, summed in fp32); None for the other metrics."""
+        if self.metric != "euclidean":
+            return None
+        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.dtype).float()
+        return t.pow(2).sum(-1).tolist()
+
     def _to_device_query(self, a: np.ndarray) -> torch.Tensor:
         t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
         if self.device.type == "cuda":
@@ -838,33 +980,41 @@ class VectorStore:
         return t.to(self.dtype)
 
     @staticmethod
-    def _build_results(hits, vec_rows) -> List[List[Dict[str, Any]]]:
+    def _build_results(hits, vec_rows, q_norm2=None) -> List[List[Dict[str, Any]]]:
         vecs = {}
         if vec_rows is not None and vec_rows[0]:
             from ..utils.fastjson import f32_rows   # native rows of float32 values
             vecs = dict(zip(vec_rows[0], f32_rows(vec_rows[1])))
         out = []
-        for row in hits:
+        for qi, row in enumerate(hits):
             res = []
             for sc, r, d in row:
-                d["similarity"] = sc
+                if q_norm2 is None:
+                    d["similarity"] = sc
+                else:
+                    d["similarity"], d["distance"] = euclidean_fields(sc, q_norm2[qi])
                 if vec_rows is not None:
                     d["vector"] = vecs.get(r)
                 res.append(d)
             out.append(res)
         return out
 
-    def rows_to_results(self, scores, rows, with_vectors: bool) -> List[List[Dict[str, Any]]]:
-        """Host results for row indices (caller holds ``lock``)."""
+    def rows_to_results(self, scores, rows, with_vectors: bool, q_norm2=None) -> List[List[Dict[str, Any]]]:
+        """Host results for row indices (caller holds ``lock``), best first.  ``q_norm2``
+        (``query_norm2``, a euclidean collection): the kernel scores become ``similarity`` and
+        ``distance`` as in ``search``; without it ``similarity`` is the score."""
         vec_rows = self.row_vectors({i for row in rows for i in row if 0 <= i < self._n}) if with_vectors else None
         out = []
-        for srow, irow in zip(scores, rows):
+        for qi, (srow, irow) in enumerate(zip(scores, rows)):
             res = []
             for sc, r in zip(srow, irow):
                 if r < 0 or r >= self._n:
                     continue
                 d = self.row_payload(r)
-                d["similarity"] = sc
+                if q_norm2 is None:
+                    d["similarity"] = sc
+                else:
+                    d["similarity"], d["distance"] = euclidean_fields(sc, q_norm2[qi])
                 if vec_rows is not None:
                     d["vector"] = vec_rows[r]
                 res.append(d)
@@ -906,9 +1056,10 @@ class VectorStore:
         return flat, arr
 
 
-def _exact_topk(X: torch.Tensor, q: torch.Tensor, k: int, chunk: int = 1 << 20, mask=None, qmask=None):
+def _exact_topk(X: torch.Tensor, q: torch.Tensor, k: int, chunk: int = 1 << 20, mask=None, qmask=None, bias=None):
     """Exact top-k by chunked GEMM + torch.topk (dims / k outside the kernel, CPU stores).
-    mask / qmask as in ``ops.knn_topk``: rows a query's mask rejects score -inf."""
+    mask / qmask as in ``ops.knn_topk``: rows a query's mask rejects score -inf.  bias (f32
+    [N]) is added to the scores in fp32, as the kernels do."""
     Qn = q.shape[0]
     best_s = torch.full((Qn, 0), float("-inf"), device=X.device)
     best_i = torch.full((Qn, 0), -1, device=X.device, dtype=torch.long)
@@ -919,6 +1070,8 @@ def _exact_topk(X: torch.Tensor, q: torch.Tensor, k: int, chunk: int = 1 << 20, 
             raise ValueError("kNN mask / qmask do not fit the store and the queries")
     for s0 in range(0, X.shape[0], chunk):
         sc = qf @ X[s0: s0 + chunk].float().t()
+        if bias is not None:
+            sc = sc + bias[s0: s0 + chunk].float()[None, :]
         if mask is not None:
             rows = torch.arange(s0, s0 + sc.shape[1], device=X.device)
             bits = ((mask[:, rows >> 5] >> (rows & 31).int()) & 1).bool()          # [M, rows]
@@ -1022,11 +1175,36 @@ class VectorStoreRegistry:
         return None
 
     @classmethod
-    def get(cls, name: str, dim: Optional[int] = None, device=None, persist: bool = True) -> VectorStore:
+    def _persisted_metric(cls, name: str) -> Optional[str]:
+        """The metric of a persisted collection (cosine when its directory predates metrics);
+        None when nothing is persisted under the name."""
+        d = cls._dir_of(name)
+        if not d or not os.path.isdir(d):
+            return None
+        m = _Persistence.read_metric(d)
+        if m is not None:
+            return canonical_metric(m)
+        return "cosine" if cls._persisted_dim(name) is not None else None
+
+    @classmethod
+    def metric_of(cls, name: str) -> Optional[str]:
+        """The metric of an existing or persisted collection; None when there is none."""
+        s = cls._stores.get(name)
+        return s.metric if s is not None else cls._persisted_metric(name)
+
+    @classmethod
+    def get(cls, name: str, dim: Optional[int] = None, device=None, persist: bool = True,
+            metric: Optional[str] = None) -> VectorStore:
         """The collection ``name`` (created with ``dim`` if new; restored from the
-        persistence directory when one is configured and ``persist``)."""
+        persistence directory when one is configured and ``persist``).  ``metric``: None for
+        whatever the collection has (cosine when it is new); a metric other than an existing
+        or persisted collection's own raises ValueError."""
+        if metric is not None:
+            metric = canonical_metric(metric)
         with cls._lock:
             s = cls._stores.get(name)
+            if s is not None and metric is not None and s.metric != metric:
+                raise ValueError(f"vector collection {name} has metric {s.metric}, not {metric}")
             if s is None:
                 if dim is None and persist:
                     dim = cls._persisted_dim(name)
@@ -1035,7 +1213,7 @@ class VectorStoreRegistry:
                 if device is None:
                     device = "cuda" if torch.cuda.is_available() else "cpu"
                 pdir = cls._dir_of(name) if persist else None
-                s = VectorStore(dim, device=device, name=name, persist_dir=pdir, fsync=cls.fsync)
+                s = VectorStore(dim, device=device, name=name, persist_dir=pdir, fsync=cls.fsync, metric=metric)
                 cls._stores[name] = s
             return s
 

@@ -524,7 +524,21 @@ def _knn_check_mask(X, Q, mask, qmask) -> torch.Tensor:
     return qm.to(torch.int32).contiguous()
 
 
-def _knn_topk_masked(X, Q, k: int, sample_chunks: Optional[int], mask, qm):
+def _knn_check_bias(X, bias) -> torch.Tensor:
+    """Validate a kNN per-row bias: a contiguous f32 [N] tensor on the device of X.  The
+    kernels read it four rows at a time, so a view that does not start on 16 bytes is copied."""
+    if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+        raise ValueError("knn_topk: bias must be a float32 tensor")
+    if bias.dim() != 1 or bias.shape[0] != X.shape[0]:
+        raise ValueError(f"knn_topk: bias must be [{X.shape[0]}] (one per row), got {tuple(bias.shape)}")
+    if bias.device != X.device or not bias.is_contiguous():
+        raise ValueError("knn_topk: bias must be contiguous and on the device of X")
+    if bias.is_cuda and bias.data_ptr() % 16:
+        bias = bias.clone()
+    return bias
+
+
+def _knn_topk_masked(X, Q, k: int, sample_chunks: Optional[int], mask, qm, bias=None):
     Qn, N = Q.shape[0], X.shape[0]
     nchunks = (N + 1023) // 1024
     dev = X.device
@@ -537,15 +551,23 @@ def _knn_topk_masked(X, Q, k: int, sample_chunks: Optional[int], mask, qm):
     ws_s = torch.empty(max(1, Qn * nchunks * k), dtype=torch.float32, device=dev)
     ws_i = torch.empty(Qn * nchunks * k + 3 * Qn, dtype=torch.int32, device=dev)
     qd = (qm.pin_memory() if dev.type == "cuda" else qm).to(dev, non_blocking=True)
-    hip().knn_topk_masked(X, Q, k, out_s, out_i, ws_s, ws_i, sample_chunks, mask, qd)
+
+    def run(sc):
+        if bias is None:
+            hip().knn_topk_masked(X, Q, k, out_s, out_i, ws_s, ws_i, sc, mask, qd)
+        else:
+            hip().knn_topk_biased(X, Q, k, out_s, out_i, ws_s, ws_i, sc, bias, mask, qd)
+
+    run(sample_chunks)
     if sample_chunks > 0 and nchunks > sample_chunks and bool(ws_i[-Qn:].any()):
         # a candidate list overflowed (a mask that admits few sample rows leaves a weak
         # threshold): exact rerun
-        hip().knn_topk_masked(X, Q, k, out_s, out_i, ws_s, ws_i, 0, mask, qd)
+        run(0)
     return out_s, out_i
 
 
-def knn_topk(X, Q, k: int, sample_chunks: Optional[int] = None, mask=None, qmask=None, _ablate: int = 0):
+def knn_topk(X, Q, k: int, sample_chunks: Optional[int] = None, mask=None, qmask=None, bias=None,
+             _ablate: int = 0):
     """Top-k rows of X by dot product with each query row.  Returns (scores f32 [Q,k], idx int32 [Q,k]).
     GPU: the first ``sample_chunks`` x 1024 rows are searched exactly and set a per-query
     threshold for the rest (0 = search every chunk exactly); ties go to the lower row.
@@ -553,15 +575,23 @@ def knn_topk(X, Q, k: int, sample_chunks: Optional[int] = None, mask=None, qmask
     ``mask`` (int32 [M, 32 * ceil(N / 1024)], bit b of word w = row 32w + b, zero bits
     past N) and ``qmask`` (host int32 [Q] or list: each query's mask row, -1 = no filter)
     restrict every query to the rows its mask admits; a query with fewer than k admitted
-    rows pads with (-inf, -1)."""
+    rows pads with (-inf, -1).
+
+    ``bias`` (f32 [N] on the device of X): the score of row r becomes ``dot + bias[r]``, added
+    in fp32 inside the kernels; with ``bias[r] = -|X[r]|^2 / 2`` the ranking is that of the
+    smallest Euclidean distance.  Thresholds, masks and the tie rule apply to that score."""
+    if bias is not None:
+        bias = _knn_check_bias(X, bias)
+        if _ablate:
+            raise ValueError("knn_topk: the timing ablations take no bias")
     if mask is not None or qmask is not None:
         qm = _knn_check_mask(X, Q, mask, qmask)
         if _ablate:
             raise ValueError("knn_topk: the timing ablations take no mask")
         if not _gpu(X):
-            return ref.knn_topk(X, Q, k, mask, qm)
+            return ref.knn_topk(X, Q, k, mask, qm, bias=bias)
         if bool((qm >= 0).any()):
-            return _knn_topk_masked(X, Q, k, sample_chunks, mask, qm)
+            return _knn_topk_masked(X, Q, k, sample_chunks, mask, qm, bias)
     if _gpu(X):
         Qn, N = Q.shape[0], X.shape[0]
         nchunks = (N + 1023) // 1024
@@ -577,9 +607,17 @@ def knn_topk(X, Q, k: int, sample_chunks: Optional[int] = None, mask=None, qmask
         if _ablate:   # tools/engine_bench.py --knn-ablate only: timing ablations, wrong results
             hip().knn_topk_ablate(X, Q, k, out_s, out_i, ws_s, ws_i, sample_chunks, _ablate)
             return out_s, out_i
-        hip().knn_topk(X, Q, k, out_s, out_i, ws_s, ws_i, sample_chunks)
+        if bias is not None and N and Qn:
+            none = torch.empty(0, dtype=torch.int32, device=dev)   # no mask
+
+            def run(sc):
+                hip().knn_topk_biased(X, Q, k, out_s, out_i, ws_s, ws_i, sc, bias, none, none)
+        else:
+            def run(sc):
+                hip().knn_topk(X, Q, k, out_s, out_i, ws_s, ws_i, sc)
+        run(sample_chunks)
         if sample_chunks > 0 and nchunks > sample_chunks and bool(ws_i[-Qn:].any()):
             # a candidate list overflowed (many rows above the sample's K-th best): exact rerun
-            hip().knn_topk(X, Q, k, out_s, out_i, ws_s, ws_i, 0)
+            run(0)
         return out_s, out_i
-    return ref.knn_topk(X, Q, k)
+    return ref.knn_topk(X, Q, k, bias=bias)

@@ -39,6 +39,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("knn_default_sample", &knn_default_sample);
   m.def("knn_topk_ablate", &knn_topk_ablate);
   m.def("knn_topk_masked", &knn_topk_masked);
+  m.def("knn_topk_biased", &knn_topk_biased);
   m.def("skinny_gemm", &skinny_gemm);
   m.def("gemv", &gemv);
   m.def("gemv_supported", &gemv_supported);

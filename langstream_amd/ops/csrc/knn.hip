@@ -24,6 +24,14 @@
 // rejects scores -inf in the exact kernel and is never appended by the main-pass kernels,
 // so the answer is the exact top-k of the admitted rows, padded with (-inf, -1) when fewer
 // than k are admitted (see knn_admitted).  The unmasked instantiations are unchanged.
+//
+// Biased search (knn_topk_biased): score(row r, query q) = dot(q, X[r]) + bias[r], bias f32 [N].
+// With bias[r] = -|X[r]|^2 / 2 the largest score is the smallest Euclidean distance
+// (|q - x|^2 = |q|^2 - 2 (q.x - |x|^2 / 2)).  In all three kernels an accumulator register is
+// a row and the lane is the query, so the BIAS instantiations start the MFMA accumulators
+// from the four biases of the lane's rows instead of zero (knn_bias4): thresholds, group
+// maxima, candidate lists, masks and the tie rule see one "higher is better" score.  The
+// instantiations without BIAS are unchanged.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "ops.h"
@@ -72,13 +80,24 @@ __device__ __forceinline__ bool knn_admitted(const int32_t* __restrict__ mask, i
   return mrow < 0 || (((uint32_t)mask[(int64_t)mrow * mw + (row >> 5)] >> (row & 31)) & 1u);
 }
 
-template <int DIM, bool MASKED = false>
+// BIAS instantiations: the biases of rows rb .. rb + 3 (rb a multiple of 4, bias 16-B aligned:
+// checked on the host), one 16-B read; zeros past N, where the vector read would leave bias.
+__device__ __forceinline__ f32x4 knn_bias4(const float* __restrict__ bias, int64_t rb, int64_t N) {
+  if (rb + 4 <= N) return *reinterpret_cast<const f32x4*>(bias + rb);
+  f32x4 b;
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) b[rr] = rb + rr < N ? bias[rb + rr] : 0.f;
+  return b;
+}
+
+template <int DIM, bool MASKED = false, bool BIAS = false>
 __global__ void __launch_bounds__(256) knn_exact_kernel(const bf16* __restrict__ X, int64_t N,
                                                          const bf16* __restrict__ Qm, int Qn, int K,
                                                          float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
                                                          int* __restrict__ ctrl, int nchunks_total, int chunk0,
                                                          int nchunks, const int32_t* __restrict__ mask,
-                                                         const int32_t* __restrict__ qmask) {
+                                                         const int32_t* __restrict__ qmask,
+                                                         const float* __restrict__ bias) {
   constexpr int KS = DIM / 32;
   constexpr int QROW = DIM + 8;   // +16 B per query row: the 16 lanes i16 of a B-fragment read hit distinct banks
   constexpr int KB = KS < 32 ? KS : 32;   // k-steps per load batch (DIM 2048: two batches)
@@ -126,7 +145,12 @@ __global__ void __launch_bounds__(256) knn_exact_kernel(const bf16* __restrict__
       for (int j = 0; j < (U + 1) / 2; ++j) mword[j] = mwp ? (uint32_t)mwp[st0 / 2 + j] : 0xFFFFFFFFu;
     }
 #pragma unroll
-    for (int u = 0; u < U; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < U; ++u) {
+      if constexpr (BIAS)
+        acc[u] = knn_bias4(bias, row0 + (st0 + u) * 16 + 4 * h, N);
+      else
+        acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 #pragma unroll
     for (int kb = 0; kb < KS; kb += KB) {
       uint4 af[U][KB];
@@ -272,13 +296,14 @@ __global__ void __launch_bounds__(256) knn_exact_kernel(const bf16* __restrict__
 // sample is the lowest rows.  A list that fills up (adversarial data: many rows above
 // the sample's K-th best) sets the query's overflow flag; the host then reruns the
 // search exactly.
-template <int DIM, bool MASKED = false>
+template <int DIM, bool MASKED = false, bool BIAS = false>
 __global__ void __launch_bounds__(256) knn_filter_kernel(const bf16* __restrict__ X, int64_t N,
                                                          const bf16* __restrict__ Qm, int Qn,
                                                          float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
                                                          int* __restrict__ ctrl, int64_t cap, int chunk0,
                                                          int nchunks, const int32_t* __restrict__ mask,
-                                                         const int32_t* __restrict__ qmask, int mw) {
+                                                         const int32_t* __restrict__ qmask, int mw,
+                                                         const float* __restrict__ bias) {
   constexpr int KS = DIM / 32;
   constexpr int QROW = DIM + 8;
   constexpr int KB = KS < 32 ? KS : 32;
@@ -317,9 +342,17 @@ __global__ void __launch_bounds__(256) knn_filter_kernel(const bf16* __restrict_
   for (int st0 = 0; st0 < 16; st0 += U) {
     f32x4 acc[U][QF / 16];
 #pragma unroll
-    for (int u = 0; u < U; ++u)
+    for (int u = 0; u < U; ++u) {
+      if constexpr (BIAS) {
+        // one read per subtile, shared by the lane's QF / 16 queries
+        const f32x4 b4 = knn_bias4(bias, row0 + (st0 + u) * 16 + 4 * h, N);
 #pragma unroll
-      for (int g = 0; g < QF / 16; ++g) acc[u][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int g = 0; g < QF / 16; ++g) acc[u][g] = b4;
+      } else {
+#pragma unroll
+        for (int g = 0; g < QF / 16; ++g) acc[u][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
 #pragma unroll
     for (int kb = 0; kb < KS; kb += KB) {
       uint4 af[U][KB];
@@ -367,6 +400,16 @@ __global__ void __launch_bounds__(256) knn_filter_kernel(const bf16* __restrict_
   }
 }
 
+// 4 B per lane from rsrc + voff into LDS at lds_addr + 4 * lane (M0-based, as blds16).
+static __device__ __forceinline__ void knn_blds4(i32x4 rsrc, int voff, unsigned lds_addr) {
+  const unsigned dst = __builtin_amdgcn_readfirstlane(lds_addr);
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(voff), "s"(rsrc), "s"(dst)
+               : "memory");
+}
+
 // Main pass for large query batches (Q >= 128, dim <= 512): 256 queries per workgroup,
 // 8 waves x 32 queries whose Q^T fragments stay in REGISTERS for the whole launch, and
 // the workgroup's row range streamed ONCE through a ring of LDS stages (64 rows each,
@@ -410,14 +453,30 @@ __global__ void __launch_bounds__(256) knn_filter_kernel(const bf16* __restrict_
 // (Q = 256 over 1M x 384, admitted 0.5 / 0.25 / 0.1: 0.457 / 0.463 / 0.489 ms here against
 // 0.501 / 0.529 / 0.554; profiles/r7/knn_filter/); it won only at 0.001 (0.69 vs 0.97 ms:
 // rejected hits never reach the LDS buffers), where the store gathers the rows instead.
-template <int DIM, int MODE, int NW = 8, int ABL = 0, bool MASKED = false>
+// BIAS (every MODE): the tile's 64 biases (256 B) ride the LDS-DMA ring with its rows -- wave 0
+// issues one 4-B-per-lane DMA per stage after its row DMAs, through a buffer resource over
+// the workgroup's bias range (biases past the range read as zeros; their rows are masked by
+// lr < nrows as before), and waits for one more outstanding operation per stage than the
+// other waves.  The ring was chosen over staging the whole range before the loop because a
+// workgroup's range is unbounded (rows_per_wg grows with N: 1M rows x 2048 queries is
+// 7.9k rows, 10M rows ten times that) while DIM 512 leaves 20 KB; the ring costs 256 B per
+// stage at any N and keeps the tile loop free of returning global loads.  A lane reads the
+// four biases of its rows (one ds_read_b128 per 16-row subtile, one subtile ahead, beside the
+// A fragments) and the accumulators of all its query groups start from them.
+// Measured over 1M x 384 (profiles/r8/knn_metric/): with a zero bias (the unbiased kernel's
+// candidates) 1.02 / 1.03 / 1.03 of the unbiased time at Q = 256 / 1024 / 2048 -- 4 more
+// ds_read_b128 on the 48 fragment reads per tile that bound this kernel; the Euclidean bias
+// itself runs at 0.96 - 0.99 (fewer scores pass the thresholds).  The tile's four bias
+// vectors read in one batch after the barrier were no faster (1.02 / 1.03 / 1.03).
+template <int DIM, int MODE, int NW = 8, int ABL = 0, bool MASKED = false, bool BIAS = false>
 __global__ void __launch_bounds__(NW * 64, 1) knn_filter_q256_kernel(const bf16* __restrict__ X, int64_t N,
                                                               const bf16* __restrict__ Qm, int Qn,
                                                               float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
                                                               int* __restrict__ ctrl, int64_t cap, int64_t row_begin,
                                                               int rows_per_wg, int nqb, float* __restrict__ gmax,
                                                               int G, int prio, const int32_t* __restrict__ mask,
-                                                              const int32_t* __restrict__ qmask, int mw) {
+                                                              const int32_t* __restrict__ qmask, int mw,
+                                                              const float* __restrict__ bias) {
   constexpr int KS = DIM / 32;
   constexpr int RB = DIM * 2;                    // bytes per row
   constexpr int TR = 64;                         // rows per LDS stage
@@ -429,7 +488,10 @@ __global__ void __launch_bounds__(NW * 64, 1) knn_filter_q256_kernel(const bf16*
   constexpr int GPW = SB / (NW * 1024);          // LDS-DMA instructions per wave per stage
   static_assert(NW == 8 || NW == 4, "waves per workgroup");
   static_assert(RB % 256 == 0 && SB % 8192 == 0, "rows must be a multiple of 256 B");
-  __shared__ __attribute__((aligned(1024))) char lds[NST * SB + CBYTES];
+  constexpr int BOFF = NST * SB + CBYTES;        // BIAS: NST bias stages of TR floats
+  constexpr int BBYTES = BIAS ? NST * TR * 4 : 0;
+  static_assert(BOFF + BBYTES <= 160 * 1024, "LDS");
+  __shared__ __attribute__((aligned(1024))) char lds[BOFF + BBYTES];
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, h = lane >> 4;
@@ -509,11 +571,15 @@ __global__ void __launch_bounds__(NW * 64, 1) knn_filter_q256_kernel(const bf16*
     voff[j] = r * RB + ((p ^ (r & 15)) * 16);
   }
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
+  i32x4 brsrc;
+  if constexpr (BIAS) brsrc = make_rsrc(bias + r0, (uint32_t)nrows * 4);
   auto issue = [&](int t, int slot) {
     const int toff = min(t, ntile - 1) * SB;   // past the end: reload the last tile (dead slot)
 #pragma unroll
     for (int j = 0; j < GPW; ++j)
       blds16(rsrc, voff[j] + toff, 0, lds_base + slot * SB + (wid * GPW + j) * 1024);
+    if constexpr (BIAS)
+      if (wid == 0) knn_blds4(brsrc, min(t, ntile - 1) * (TR * 4) + lane * 4, lds_base + BOFF + slot * (TR * 4));
   };
   // A fragment of 16-row subtile i, k-step ks: row 16i + fr, chunk 4ks + h (swizzled)
   int aoff[KS];
@@ -524,10 +590,16 @@ __global__ void __launch_bounds__(NW * 64, 1) knn_filter_q256_kernel(const bf16*
   // compare / ballot / append is issued after subtile i+1's MFMAs, so the wave never waits
   // on an MFMA result it has just requested (two accumulator sets alternate; the last
   // subtile of a tile is checked after the next tile's first MFMAs).
-  auto mm = [&](const bf16x8 (&f)[KS], f32x4 (&acc)[QGW]) {
+  // b: BIAS only -- the biases of the lane's four rows of the subtile, where the sums start
+  auto mm = [&](const bf16x8 (&f)[KS], f32x4 (&acc)[QGW], const f32x4& b) {
     if (prio == 2) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int g = 0; g < QGW; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int g = 0; g < QGW; ++g) {
+      if constexpr (BIAS)
+        acc[g] = b;
+      else
+        acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
@@ -588,7 +660,15 @@ __global__ void __launch_bounds__(NW * 64, 1) knn_filter_q256_kernel(const bf16*
   for (int s = 0; s < NST - 1; ++s) issue(s, s);
   for (int t = 0; t < ntile; ++t) {
     if constexpr (ABL != 1 && ABL != 2) {
-      wait_vmcnt<(NST - 2) * GPW>();   // this wave's DMA of tile t landed (tiles t+1.. may be in flight)
+      // this wave's DMA of tile t landed (tiles t+1.. may be in flight)
+      if constexpr (BIAS) {
+        if (wid == 0)
+          wait_vmcnt<(NST - 2) * (GPW + 1)>();   // wave 0 also carries the stage's bias DMA
+        else
+          wait_vmcnt<(NST - 2) * GPW>();
+      } else {
+        wait_vmcnt<(NST - 2) * GPW>();
+      }
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();    // every wave's part of tile t landed; tile t-1's slot is free
       __builtin_amdgcn_sched_barrier(0);
@@ -599,23 +679,26 @@ __global__ void __launch_bounds__(NW * 64, 1) knn_filter_q256_kernel(const bf16*
     // A fragments double-buffered across the tile's four 16-row subtiles: subtile i+1's
     // LDS reads are in flight while subtile i's MFMAs run
     bf16x8 fa[KS], fb[KS];
-    auto rd = [&](int i, bf16x8 (&f)[KS]) {
+    f32x4 ba, bb;   // BIAS: the subtiles' biases, read with their fragments
+    const char* bst = lds + BOFF + (t % NST) * (TR * 4) + 16 * h;
+    auto rd = [&](int i, bf16x8 (&f)[KS], f32x4& b) {
+      if constexpr (BIAS) b = *reinterpret_cast<const f32x4*>(bst + i * 64);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) f[ks] = __builtin_bit_cast(bf16x8, ld16(st + i * 16 * RB + aoff[ks]));
     };
     if constexpr (DIM > 384) {
       // one fragment set: two of them beside the query fragments exceed 256 VGPRs
-      rd(0, fa);
-      mm(fa, accA);
+      rd(0, fa, ba);
+      mm(fa, accA, ba);
       if (pend >= 0) epi(pend, accB);
-      rd(1, fa);
-      mm(fa, accB);
+      rd(1, fa, ba);
+      mm(fa, accB, ba);
       epi(tl0, accA);
-      rd(2, fa);
-      mm(fa, accA);
+      rd(2, fa, ba);
+      mm(fa, accA, ba);
       epi(tl0 + 16, accB);
-      rd(3, fa);
-      mm(fa, accB);
+      rd(3, fa, ba);
+      mm(fa, accB, ba);
       epi(tl0 + 32, accA);
       pend = tl0 + 48;
       continue;
@@ -626,10 +709,21 @@ __global__ void __launch_bounds__(NW * 64, 1) knn_filter_q256_kernel(const bf16*
       // all-read or all-MFMA phase (sched_group_barrier, one sync group).  Q = 2048: 1.585
       // vs 1.635 ms for reads pinned ahead of each subtile (profiles/knn_ilv_r4y/, with the
       // MFMA clusters at raised priority)
-      auto mmrd = [&](const bf16x8 (&f)[KS], f32x4 (&acc)[QGW], bf16x8 (&nf)[KS], int inext) {
+      auto mmrd = [&](const bf16x8 (&f)[KS], f32x4 (&acc)[QGW], const f32x4& b, bf16x8 (&nf)[KS], f32x4& nb,
+                      int inext) {
         if (prio == 2) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-        for (int g = 0; g < QGW; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int g = 0; g < QGW; ++g) {
+          if constexpr (BIAS)
+            acc[g] = b;
+          else
+            acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        if constexpr (BIAS) {
+          // the next subtile's biases: one more ds_read, ahead of the interleaved groups
+          nb = *reinterpret_cast<const f32x4*>(bst + inext * 64);
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           nf[ks] = __builtin_bit_cast(bf16x8, ld16(st + inext * 16 * RB + aoff[ks]));
@@ -644,14 +738,14 @@ __global__ void __launch_bounds__(NW * 64, 1) knn_filter_q256_kernel(const bf16*
         }
         if (prio == 2) __builtin_amdgcn_s_setprio(0);
       };
-      rd(0, fa);
-      mmrd(fa, accA, fb, 1);              // subtile 0, reads 1
+      rd(0, fa, ba);
+      mmrd(fa, accA, ba, fb, bb, 1);      // subtile 0, reads 1
       if (pend >= 0) epi(pend, accB);
-      mmrd(fb, accB, fa, 2);              // subtile 1, reads 2
+      mmrd(fb, accB, bb, fa, ba, 2);      // subtile 1, reads 2
       epi(tl0, accA);
-      mmrd(fa, accA, fb, 3);              // subtile 2, reads 3
+      mmrd(fa, accA, ba, fb, bb, 3);      // subtile 2, reads 3
       epi(tl0 + 16, accB);
-      mm(fb, accB);                       // subtile 3
+      mm(fb, accB, bb);                   // subtile 3
       epi(tl0 + 32, accA);
       pend = tl0 + 48;
       continue;
@@ -659,23 +753,23 @@ __global__ void __launch_bounds__(NW * 64, 1) knn_filter_q256_kernel(const bf16*
     // sched_barriers pin each subtile's reads ahead of the previous subtile's MFMAs:
     // left alone, hipcc sinks every read to just before its MFMA behind an lgkmcnt wait
 #define KNN_SB __builtin_amdgcn_sched_barrier(0)
-    rd(0, fa);
-    rd(1, fb);
+    rd(0, fa, ba);
+    rd(1, fb, bb);
     KNN_SB;
-    mm(fa, accA);                       // subtile 0
+    mm(fa, accA, ba);                   // subtile 0
     if (pend >= 0) epi(pend, accB);     // the previous tile's subtile 3
     KNN_SB;
-    rd(2, fa);
+    rd(2, fa, ba);
     KNN_SB;
-    mm(fb, accB);                       // subtile 1
+    mm(fb, accB, bb);                   // subtile 1
     epi(tl0, accA);
     KNN_SB;
-    rd(3, fb);
+    rd(3, fb, bb);
     KNN_SB;
-    mm(fa, accA);                       // subtile 2
+    mm(fa, accA, ba);                   // subtile 2
     epi(tl0 + 16, accB);
     KNN_SB;
-    mm(fb, accB);                       // subtile 3
+    mm(fb, accB, bb);                   // subtile 3
     epi(tl0 + 32, accA);
 #undef KNN_SB
     pend = tl0 + 48;
@@ -715,37 +809,51 @@ __global__ void __launch_bounds__(256) knn_group_thr_kernel(const float* __restr
 template <int DD, int MM>
 void launch_q256(int abl, dim3 grid, hipStream_t stream, const bf16* X, int64_t N, const bf16* Q, int Qn, float* ws_s,
                  int32_t* ws_i, int* ctrl, int64_t cap, int64_t row_begin, int rpw, int nqb, int G,
-                 const int32_t* mask, const int32_t* qmask, int mw) {
+                 const int32_t* mask, const int32_t* qmask, int mw, const float* bias) {
   // LS_KNN_PRIO: 2 (default) MFMA clusters at raised priority, 1 half the waves raised, 0 none
   static const int prio = env_int("LS_KNN_PRIO", 2);
   if constexpr (MM == 0) {
-    if (mask) {
-      knn_filter_q256_kernel<DD, 0, 8, 0, true><<<grid, 512, 0, stream>>>(X, N, Q, Qn, ws_s, ws_i, ctrl, cap, row_begin,
-                                                                         rpw, nqb, ws_s, G, prio, mask, qmask, mw);
+    if (mask && bias) {
+      knn_filter_q256_kernel<DD, 0, 8, 0, true, true><<<grid, 512, 0, stream>>>(
+          X, N, Q, Qn, ws_s, ws_i, ctrl, cap, row_begin, rpw, nqb, ws_s, G, prio, mask, qmask, mw, bias);
       return;
     }
+    if (mask) {
+      knn_filter_q256_kernel<DD, 0, 8, 0, true><<<grid, 512, 0, stream>>>(X, N, Q, Qn, ws_s, ws_i, ctrl, cap, row_begin,
+                                                                         rpw, nqb, ws_s, G, prio, mask, qmask, mw,
+                                                                         nullptr);
+      return;
+    }
+  }
+  if (bias) {   // the timing ablations take no bias
+    knn_filter_q256_kernel<DD, MM, 8, 0, false, true><<<grid, 512, 0, stream>>>(
+        X, N, Q, Qn, ws_s, ws_i, ctrl, cap, row_begin, rpw, nqb, ws_s, G, prio, nullptr, nullptr, 0, bias);
+    return;
   }
   // the timing-only ablations exist for the bench's shape (384 dims, main pass) only
   if constexpr (DD == 384 && MM == 1) {
     switch (abl) {
       case 1:
         knn_filter_q256_kernel<DD, MM, 8, 1><<<grid, 512, 0, stream>>>(X, N, Q, Qn, ws_s, ws_i, ctrl, cap, row_begin,
-                                                                       rpw, nqb, ws_s, G, prio, nullptr, nullptr, 0);
+                                                                       rpw, nqb, ws_s, G, prio, nullptr, nullptr, 0,
+                                                                       nullptr);
         return;
       case 2:
         knn_filter_q256_kernel<DD, MM, 8, 2><<<grid, 512, 0, stream>>>(X, N, Q, Qn, ws_s, ws_i, ctrl, cap, row_begin,
-                                                                       rpw, nqb, ws_s, G, prio, nullptr, nullptr, 0);
+                                                                       rpw, nqb, ws_s, G, prio, nullptr, nullptr, 0,
+                                                                       nullptr);
         return;
       case 3:
         knn_filter_q256_kernel<DD, MM, 8, 3><<<grid, 512, 0, stream>>>(X, N, Q, Qn, ws_s, ws_i, ctrl, cap, row_begin,
-                                                                       rpw, nqb, ws_s, G, prio, nullptr, nullptr, 0);
+                                                                       rpw, nqb, ws_s, G, prio, nullptr, nullptr, 0,
+                                                                       nullptr);
         return;
       default:
         break;
     }
   }
   knn_filter_q256_kernel<DD, MM, 8><<<grid, 512, 0, stream>>>(X, N, Q, Qn, ws_s, ws_i, ctrl, cap, row_begin, rpw, nqb,
-                                                              ws_s, G, prio, nullptr, nullptr, 0);
+                                                              ws_s, G, prio, nullptr, nullptr, 0, nullptr);
 }
 
 __global__ void knn_init_kernel(int* __restrict__ ctrl, int Qn) {
@@ -880,7 +988,7 @@ __global__ void __launch_bounds__(256) knn_select4_kernel(const float* __restric
 
 }  // namespace
 
-// X: [N, dim] bf16 (rows L2-normalised), Q: [Qn, dim] bf16.  Returns via out tensors
+// X: [N, dim] bf16 (L2-normalised for cosine similarity), Q: [Qn, dim] bf16.  Returns via out tensors
 // the top-K scores (f32 [Qn, K]) and row indices (int32 [Qn, K], -1 if N < K).
 // workspace: f32 [Qn * nchunks * K] and int32 [Qn * nchunks * K + 3 * Qn] (candidate
 // lists, then per-query candidate counts, thresholds and overflow flags).
@@ -892,7 +1000,7 @@ __global__ void __launch_bounds__(256) knn_select4_kernel(const float* __restric
 namespace {
 void knn_topk_impl(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::Tensor out_i, at::Tensor ws_s,
                    at::Tensor ws_i, int64_t sample, int abl_req, const int32_t* mask = nullptr,
-                   const int32_t* qmask = nullptr) {
+                   const int32_t* qmask = nullptr, const float* bias = nullptr) {
   TORCH_CHECK(X.scalar_type() == at::kBFloat16 && Q.scalar_type() == at::kBFloat16);
   TORCH_CHECK(X.is_contiguous() && Q.is_contiguous() && X.dim() == 2 && Q.dim() == 2);
   const int dim = X.size(1);
@@ -926,17 +1034,22 @@ void knn_topk_impl(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::
   }
   auto exact = [&](int nc) {
     dim3 grid(nc * nqg);
-#define LAUNCH_E(DD)                                                                                            \
-  if (mask)                                                                                                     \
-    knn_exact_kernel<DD, true><<<grid, 256, 0, stream>>>(                                                       \
-        (const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(), Qn, (int)K, ws_s.data_ptr<float>(),            \
-        ws_i.data_ptr<int32_t>(), ctrl, nchunks, 0, nc, mask, qmask);                                           \
-  else                                                                                                          \
-    knn_exact_kernel<DD><<<grid, 256, 0, stream>>>((const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(),    \
-                                                   Qn, (int)K, ws_s.data_ptr<float>(), ws_i.data_ptr<int32_t>(), \
-                                                   ctrl, nchunks, 0, nc, nullptr, nullptr)
+#define LAUNCH_EB(DD, MK, BS)                                                                                   \
+  knn_exact_kernel<DD, MK, BS><<<grid, 256, 0, stream>>>(                                                       \
+      (const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(), Qn, (int)K, ws_s.data_ptr<float>(),              \
+      ws_i.data_ptr<int32_t>(), ctrl, nchunks, 0, nc, mask, qmask, bias)
+#define LAUNCH_E(DD)                  \
+  if (mask && bias)                   \
+    LAUNCH_EB(DD, true, true);        \
+  else if (mask)                      \
+    LAUNCH_EB(DD, true, false);       \
+  else if (bias)                      \
+    LAUNCH_EB(DD, false, true);       \
+  else                                \
+    LAUNCH_EB(DD, false, false)
     DISPATCH_DIM(LAUNCH_E)
 #undef LAUNCH_E
+#undef LAUNCH_EB
   };
   static const int q256_min = env_int("LS_KNN_Q256_MIN", 128);
   const bool q256 = Qn >= q256_min && (dim == 128 || dim == 256 || dim == 384 || dim == 512);
@@ -959,7 +1072,7 @@ void knn_topk_impl(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::
 #define LAUNCH_Q(DD, MM)                                                                                         \
   launch_q256<DD, MM>(abl, grid, stream, (const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(), Qn,            \
                       ws_s.data_ptr<float>(), ws_i.data_ptr<int32_t>(), ctrl, cap, row_begin, (int)rpw, nqb, G,     \
-                      mask, qmask, mw)
+                      mask, qmask, mw, bias)
 #define LAUNCH_QM(DD)                     \
   switch (mode) {                         \
     case 0: LAUNCH_Q(DD, 0); break;       \
@@ -985,17 +1098,22 @@ void knn_topk_impl(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::
       return;
     }
     dim3 grid(nc * nqf);
-#define LAUNCH_F(DD)                                                                                              \
-  if (mask)                                                                                                       \
-    knn_filter_kernel<DD, true><<<grid, 256, 0, stream>>>(                                                        \
-        (const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(), Qn, ws_s.data_ptr<float>(),                      \
-        ws_i.data_ptr<int32_t>(), ctrl, cap, c0, nc, mask, qmask, mw);                                            \
-  else                                                                                                            \
-    knn_filter_kernel<DD><<<grid, 256, 0, stream>>>((const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(), Qn, \
-                                                    ws_s.data_ptr<float>(), ws_i.data_ptr<int32_t>(), ctrl, cap,  \
-                                                    c0, nc, nullptr, nullptr, 0)
+#define LAUNCH_FB(DD, MK, BS)                                                                  \
+  knn_filter_kernel<DD, MK, BS><<<grid, 256, 0, stream>>>(                                     \
+      (const bf16*)X.data_ptr(), N, (const bf16*)Q.data_ptr(), Qn, ws_s.data_ptr<float>(),     \
+      ws_i.data_ptr<int32_t>(), ctrl, cap, c0, nc, mask, qmask, mask ? mw : 0, bias)
+#define LAUNCH_F(DD)                  \
+  if (mask && bias)                   \
+    LAUNCH_FB(DD, true, true);        \
+  else if (mask)                      \
+    LAUNCH_FB(DD, true, false);       \
+  else if (bias)                      \
+    LAUNCH_FB(DD, false, true);       \
+  else                                \
+    LAUNCH_FB(DD, false, false)
     DISPATCH_DIM(LAUNCH_F)
 #undef LAUNCH_F
+#undef LAUNCH_FB
   };
 #undef DISPATCH_DIM
   auto select = [&](int write_thr) {
@@ -1055,6 +1173,31 @@ void knn_topk_masked(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at
               32 * nchunks, "]");
   TORCH_CHECK(qmask.dim() == 1 && qmask.size(0) == Q.size(0), "kNN qmask must be [Q]");
   knn_topk_impl(X, Q, K, out_s, out_i, ws_s, ws_i, sample, 0, mask.data_ptr<int32_t>(), qmask.data_ptr<int32_t>());
+}
+
+// Biased search: score = dot + bias[row] (bias f32 [N]; see the file comment).  mask / qmask as
+// in knn_topk_masked, or both empty tensors for an unfiltered search.
+void knn_topk_biased(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::Tensor out_i, at::Tensor ws_s,
+                     at::Tensor ws_i, int64_t sample, at::Tensor bias, at::Tensor mask, at::Tensor qmask) {
+  TORCH_CHECK(X.dim() == 2 && Q.dim() == 2);
+  TORCH_CHECK(bias.scalar_type() == at::kFloat && bias.is_contiguous() && bias.device() == X.device() &&
+                  bias.numel() == X.size(0),
+              "kNN bias must be a contiguous f32 [N] on the device of X");
+  TORCH_CHECK(bias.numel() == 0 || (uintptr_t)bias.data_ptr<float>() % 16 == 0, "kNN bias must be 16-byte aligned");
+  const float* bp = bias.numel() ? bias.data_ptr<float>() : nullptr;
+  if (mask.numel() == 0 && qmask.numel() == 0) {
+    knn_topk_impl(X, Q, K, out_s, out_i, ws_s, ws_i, sample, 0, nullptr, nullptr, bp);
+    return;
+  }
+  const int64_t nchunks = (X.size(0) + CH - 1) / CH;
+  TORCH_CHECK(mask.scalar_type() == at::kInt && qmask.scalar_type() == at::kInt, "kNN mask / qmask must be int32");
+  TORCH_CHECK(mask.is_contiguous() && qmask.is_contiguous() && mask.device() == X.device() &&
+              qmask.device() == X.device());
+  TORCH_CHECK(mask.dim() == 2 && mask.size(0) >= 1 && mask.size(1) == 32 * nchunks, "kNN mask must be [M, ",
+              32 * nchunks, "]");
+  TORCH_CHECK(qmask.dim() == 1 && qmask.size(0) == Q.size(0), "kNN qmask must be [Q]");
+  knn_topk_impl(X, Q, K, out_s, out_i, ws_s, ws_i, sample, 0, mask.data_ptr<int32_t>(), qmask.data_ptr<int32_t>(),
+                bp);
 }
 
 // Timing-only ablations of the large-batch main pass (tools/engine_bench.py --knn-ablate):

@@ -126,6 +126,8 @@ void knn_topk(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::Tenso
               at::Tensor ws_i, int64_t sample);
 void knn_topk_masked(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::Tensor out_i, at::Tensor ws_s,
                      at::Tensor ws_i, int64_t sample, at::Tensor mask, at::Tensor qmask);
+void knn_topk_biased(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::Tensor out_i, at::Tensor ws_s,
+                     at::Tensor ws_i, int64_t sample, at::Tensor bias, at::Tensor mask, at::Tensor qmask);
 void knn_topk_ablate(at::Tensor X, at::Tensor Q, int64_t K, at::Tensor out_s, at::Tensor out_i, at::Tensor ws_s,
                      at::Tensor ws_i, int64_t sample, int64_t abl);
 int64_t knn_default_sample();

@@ -264,8 +264,10 @@ def knn_admitted(mask, qmask, Qn: int, N: int):
     return adm
 
 
-def knn_topk(X, Q, k, mask=None, qmask=None):
+def knn_topk(X, Q, k, mask=None, qmask=None, bias=None):
     s = Q.float() @ X.float().t()
+    if bias is not None:   # score = dot + bias[row], in fp32
+        s = s + bias.float().to(s.device)[None, :]
     if mask is not None:
         s = s.masked_fill(~knn_admitted(mask, qmask, Q.shape[0], X.shape[0]).to(s.device), float("-inf"))
     kk = min(k, X.shape[0])

@@ -118,10 +118,38 @@ def bench_knn(args):
 
     from langstream_amd import ops
     from langstream_amd.engine.vector_store import pack_mask
-    X = torch.nn.functional.normalize(torch.randn(args.rows, 384, device="cuda"), dim=-1).bfloat16()
+    X = torch.nn.functional.normalize(torch.randn(args.rows, 384, device="cuda"), dim=-1)
+    if args.knn_metric != "cosine":   # rows of different lengths: unit vectors x [0.5, 2]
+        X = X * (0.5 + 1.5 * torch.rand(args.rows, 1, device="cuda"))
+    X = X.bfloat16()
     fracs = [float(f) for f in str(args.knn_filter_frac).split(",") if f]
     for nq in str(args.queries).split(","):
-        Q = torch.nn.functional.normalize(torch.randn(int(nq), 384, device="cuda"), dim=-1).bfloat16()
+        Q = torch.nn.functional.normalize(torch.randn(int(nq), 384, device="cuda"), dim=-1)
+        if args.knn_metric != "cosine":
+            Q = Q * (0.5 + 1.5 * torch.rand(int(nq), 1, device="cuda"))
+        Q = Q.bfloat16()
+        if args.knn_metric == "euclidean":
+            # the biased kernels (score = dot - |x|^2 / 2) next to the unbiased ones on the same
+            # X and Q, interleaved in this process: medians over the rounds, and the spread of
+            # the unbiased rounds to judge the ratio against.  A zero bias runs the biased
+            # kernels on the unbiased scores: the same candidates, so the kernels' own cost
+            # (the Euclidean scores pass the thresholds at another rate than the dot products)
+            bias = X.float().pow(2).sum(-1).mul(-0.5).contiguous()
+            zero = torch.zeros_like(bias)
+            tu, tb, tz = [], [], []
+            for _ in range(max(3, args.knn_rounds)):
+                tu.append(_time_ms(lambda: ops.knn_topk(X, Q, 20)))
+                tb.append(_time_ms(lambda: ops.knn_topk(X, Q, 20, bias=bias)))
+                tz.append(_time_ms(lambda: ops.knn_topk(X, Q, 20, bias=zero)))
+            mu, mb, mz = float(np.median(tu)), float(np.median(tb)), float(np.median(tz))
+            print(json.dumps({"test": "knn_metric", "metric": "euclidean", "rows": args.rows, "queries": int(nq),
+                              "unbiased_ms": round(mu, 4), "biased_ms": round(mb, 4),
+                              "biased_over_unbiased": round(mb / mu, 4), "zero_bias_ms": round(mz, 4),
+                              "zero_bias_over_unbiased": round(mz / mu, 4),
+                              "unbiased_rounds_ms": [round(t, 4) for t in tu],
+                              "biased_rounds_ms": [round(t, 4) for t in tb],
+                              "unbiased_spread": round((max(tu) - min(tu)) / mu, 4)}), flush=True)
+            continue
         ms = _time_ms(lambda: ops.knn_topk(X, Q, 20, _ablate=args.knn_ablate))
         print(json.dumps({"test": "knn", "rows": args.rows, "queries": int(nq), "ms": round(ms, 3),
                           "GB_per_s": round(args.rows * 384 * 2 / ms / 1e6, 1)}), flush=True)
@@ -158,6 +186,10 @@ if __name__ == "__main__":
     ap.add_argument("--queries", default="64", help="comma-separated query counts (knn)")
     ap.add_argument("--knn-ablate", type=int, default=0,
                     help="kNN main-pass timing ablation 1-3 (diagnosis only: WRONG results)")
+    ap.add_argument("--knn-metric", choices=("cosine", "dot-product", "euclidean"), default="cosine",
+                    help="kNN data and scoring: cosine (unit rows), dot-product (rows of different lengths, the same "
+                         "kernels), euclidean (the per-row bias: biased and unbiased times and their ratio)")
+    ap.add_argument("--knn-rounds", type=int, default=3, help="interleaved rounds of --knn-metric euclidean (>= 3)")
     ap.add_argument("--knn-filter-frac", default="",
                     help="comma-separated admitted fractions: also time the filtered search (masked kernels and "
                          "compact route) next to the unfiltered one, e.g. 0.5,0.1")
