@@ -23,6 +23,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "ops.h"
+#include <cfloat>
 
 namespace {
 
@@ -55,8 +56,10 @@ __device__ __forceinline__ uint32_t row_key(uint64_t seed) {
 
 __device__ __forceinline__ float uniform01(uint32_t key, uint32_t idx) {
   const uint32_t z = hash32(idx * 0x9e3779b9U + key);
-  // 24 random bits -> (0, 1)
-  return ((float)(z >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  // 24 random bits -> (0, 1).  Above 2^23 the f32 sum rounds to even, so 0xffffff + 0.5
+  // becomes 2^24: without the clamp that draw is u = 1, its Gumbel noise +inf, and the
+  // element wins whatever its logit (once in 2^24 draws: ~1 row in 130 at V = 128K).
+  return fminf(((float)(z >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
 }
 
 template <typename T>
@@ -136,7 +139,9 @@ __global__ void __launch_bounds__(1024) sample_kernel(const T* __restrict__ logi
 
   // ---- pass 1: max, argmax, sum exp (T = 1)
   ArgMax best{-INFINITY, 0x7fffffff};
-  float mloc = -INFINITY, sloc = 0.f;
+  // The running maximum starts at -FLT_MAX, not -inf: a masked (-inf) logit then falls
+  // into the else branch as exp(-inf) = 0 instead of exp(-inf - -inf) = NaN.
+  float mloc = -FLT_MAX, sloc = 0.f;
   sweep(lr, V, aligned, [&](float x, int i) {
     if (x > best.v) best = ArgMax{x, i};
     if (x > mloc) {
@@ -174,7 +179,9 @@ __global__ void __launch_bounds__(1024) sample_kernel(const T* __restrict__ logi
   for (int w = 0; w < nw; ++w) gs += red_m[w] == -INFINITY ? 0.f : red_s[w] * __expf(red_m[w] - gm);
   const float logZ = gm + __logf(gs);
 
-  int token = gbest.i;
+  // a row with no finite maximum (all -inf / NaN) leaves gbest.i at its sentinel: emit token 0
+  // rather than index past the row (the top-n loop below clamps the same way)
+  int token = gbest.i < V ? gbest.i : 0;
   if (!greedy) {
     const int k = top_k[row];
     const float p = top_p[row];
@@ -263,7 +270,7 @@ __global__ void __launch_bounds__(1024) sample_kernel(const T* __restrict__ logi
     __syncthreads();
     ArgMax gg{-INFINITY, 0x7fffffff};
     for (int w = 0; w < nw; ++w) gg = amax(gg, ArgMax{red_f[w], red_i[w]});
-    token = gg.i < V ? gg.i : gbest.i;
+    if (gg.i < V) token = gg.i;
   }
   if (tid == 0) {
     out_tok[row] = token;
@@ -299,6 +306,22 @@ __global__ void __launch_bounds__(1024) sample_kernel(const T* __restrict__ logi
   }
 }
 
+__device__ __forceinline__ void logit_add(float* p, float d) { atomicAdd(p, d); }
+
+// bf16 has no atomic add: compare-and-swap the aligned 32-bit word that holds the element
+__device__ __forceinline__ void logit_add(bf16* p, float d) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  unsigned int* w = reinterpret_cast<unsigned int*>(a & ~(uintptr_t)3);
+  const int sh = (a & 2) ? 16 : 0;
+  unsigned int old = *w, seen;
+  do {
+    seen = old;
+    const bf16 cur = __builtin_bit_cast(bf16, (unsigned short)(seen >> sh));
+    const unsigned int nv = __builtin_bit_cast(unsigned short, (bf16)((float)cur + d));
+    old = atomicCAS(w, seen, (seen & ~(0xffffu << sh)) | (nv << sh));
+  } while (old != seen);
+}
+
 template <typename T>
 __global__ void penalty_kernel(T* __restrict__ logits, int64_t row_stride, int V, const int32_t* __restrict__ rows,
                                const int32_t* __restrict__ toks, const float* __restrict__ delta, int n) {
@@ -306,8 +329,8 @@ __global__ void penalty_kernel(T* __restrict__ logits, int64_t row_stride, int V
   if (i >= n) return;
   const int t = toks[i];
   if (t < 0 || t >= V) return;
-  T* p = logits + (int64_t)rows[i] * row_stride + t;
-  *p = (T)((float)(*p) + delta[i]);
+  // several triples of one call may name the same (row, tok): accumulate atomically
+  logit_add(logits + (int64_t)rows[i] * row_stride + t, delta[i]);
 }
 
 
@@ -342,7 +365,7 @@ __global__ void __launch_bounds__(1024) tp_stats_kernel(const float* __restrict_
   const float* lr = logits + (int64_t)row * row_stride;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nw = blockDim.x >> 6;
   ArgMax best{-INFINITY, 0x7fffffff};
-  float m = -INFINITY, sm = 0.f;
+  float m = -FLT_MAX, sm = 0.f;  // as in sample_kernel: a masked logit adds exp(-inf) = 0
   sweep(lr, Vl, aligned, [&](float x, int i) {
     if (x > best.v) best = ArgMax{x, i};
     if (x > m) {
@@ -587,7 +610,7 @@ __global__ void tp_final_kernel(const float* __restrict__ stats_all, const float
   if (row >= R) return;
   const int CW = 3 + 2 * n_top;
   const RowStats st = row_stats(stats_all, W, R, row);
-  int token = st.best.i;
+  int token = st.best.i == 0x7fffffff ? 0 : st.best.i;  // no finite maximum on any rank: as sample_kernel
   float x = st.best.v;
   if (temperature[row] > 0.f) {
     ArgMax g{-INFINITY, 0x7fffffff};

@@ -327,6 +327,41 @@ def test_pooling(mode):
     _close(got, exp, 2e-3, 1e-2)
 
 
+@pytest.mark.parametrize("out_dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("normalize", [True, False])
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("H", [8, 1024])
+def test_pooling_shapes(H, mode, normalize, out_dtype):
+    # lengths below the four waves of a block (1, 2, 3), equal to them, one past them, and many
+    # rounds (257); H = 8 is one 16-B vector (one lane), H = 1024 the kernel's maximum
+    torch.manual_seed(41)
+    lens = [1, 2, 3, 4, 5, 257]
+    x = torch.randn(sum(lens) + 3, H, device=DEV, dtype=torch.bfloat16)
+    st = torch.tensor([0, 1, 3, 6, 10, 15], dtype=torch.int32, device=DEV)
+    ln = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    got = ops.pool_embeddings(x, st, ln, mode, normalize, out_dtype=out_dtype)
+    assert got.dtype == out_dtype and got.shape == (len(lens), H)
+    exp = ref.pool_embeddings(x.cpu(), st.cpu(), ln.cpu(), mode, normalize)
+    _close(got, exp, 2e-3, 1e-2)
+
+
+@pytest.mark.parametrize("H", [8, 384, 1024, 4096])
+@pytest.mark.parametrize("rows", [1, 4, 5, 1001])
+def test_l2_normalize_rows(rows, H):
+    # one wave per row, four rows per block: 1 / 5 / 1001 rows leave a part-filled last block
+    torch.manual_seed(42)
+    x = (torch.randn(rows, H) * 3).bfloat16()
+    zero = rows // 2 if rows > 1 else None
+    if zero is not None:
+        x[zero] = 0                 # an all-zero row gives zeros, not NaN
+    got = ops.l2_normalize_rows(x.to(DEV))
+    assert got.dtype == torch.bfloat16 and got.shape == x.shape
+    xd = x.double()
+    exp = (xd / xd.norm(dim=-1, keepdim=True).clamp_min(1e-12)).bfloat16()
+    assert torch.isfinite(got).all() and (zero is None or (got[zero] == 0).all())
+    _close(got, exp, 0.02, 0.02)
+
+
 @pytest.mark.parametrize("N,Qn,k,dup", [(5000, 3, 20, 0), (1024, 20, 5, 0), (10, 2, 20, 0), (70000, 40, 64, 0),
                                          (100000, 17, 20, 0), (4096, 5, 20, 7), (3000, 4, 64, 50),
                                          (200000, 256, 20, 0), (50000, 64, 64, 3)])
