@@ -101,6 +101,18 @@ def llama3_chat_prompt(messages: List[ChatMessage]) -> str:
     return "".join(out)
 
 
+def chatml_chat_prompt(messages: List[ChatMessage]) -> str:
+    """ChatML (Qwen2): ``<|im_start|>{role}\n{content}<|im_end|>\n`` per message, then the
+    open assistant turn."""
+    out = [f"<|im_start|>{m.role}\n{m.content}<|im_end|>\n" for m in messages]
+    out.append("<|im_start|>assistant\n")
+    return "".join(out)
+
+
+# the engine's ``chat_template`` (local-gpu-configuration ``chat-template``) -> prompt function
+CHAT_TEMPLATES = {"llama3": llama3_chat_prompt, "chatml": chatml_chat_prompt}
+
+
 def _sampling_from_options(options: Dict[str, Any], tok):
     from ...engine.llm_engine import SamplingParams
     stop = options.get("stop") or []
@@ -167,7 +179,8 @@ class LocalCompletionsService(CompletionsService):
         return fut
 
     def get_chat_completions(self, messages, consumer, options) -> Future:
-        return self._submit(llama3_chat_prompt(messages), consumer, options, False)
+        prompt = CHAT_TEMPLATES[getattr(self.engine, "chat_template", "llama3")]
+        return self._submit(prompt(messages), consumer, options, False)
 
     def get_text_completions(self, prompts, consumer, options) -> Future:
         return self._submit("\n".join(prompts), consumer, options, bool(options.get("logprobs")))

@@ -330,7 +330,13 @@ RESOURCE_MODELS: Dict[str, Model] = {
         "region": S("Region.", default="us-east-1"), "endpoint-override": S("Endpoint override.")}),
     "local-gpu-configuration": Model("Local GPU engine", "In-process MI355X engines (Llama decode + embeddings).", {
         "model": S("Chat/completion model config name."), "embeddings-model": S("Embedding model config name."),
-        "checkpoint": S("Safetensors checkpoint directory."), "tp": I("Tensor-parallel degree."),
+        "checkpoint": S("Safetensors checkpoint directory."),
+        "model-path": S("Hugging Face model directory (config.json, *.safetensors, tokenizer.json) of a llama, "
+                        "mistral or qwen2 model: shape, weights and tokenizer come from it, and it serves every "
+                        "local chat and text completion."),
+        "chat-template": S("Chat prompt format: llama3 or chatml; unset: chatml for a qwen2 model-path, else "
+                           "llama3."),
+        "tp": I("Tensor-parallel degree."),
         "max-batch": I("Max concurrent sequences."), "max-seq-len": I("Max sequence length."),
         "kv-cache-dtype": S("Paged KV cache element type: auto (the model dtype), bf16 or fp8 (e4m3, twice the "
                             "tokens per kv-fraction); unset: the LS_KV_CACHE_DTYPE environment variable, else auto."),

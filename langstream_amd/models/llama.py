@@ -47,6 +47,7 @@ class LlamaConfig:
     tie_embeddings: bool = False
     bos_token_id: int = 128000
     eos_token_ids: tuple = (128001, 128009)
+    qkv_bias: bool = False   # a bias on the fused QKV projection (Qwen2), added before RoPE
 
     @property
     def num_params(self) -> int:
@@ -54,6 +55,8 @@ class LlamaConfig:
         qkv = H * (self.num_heads + 2 * self.num_kv_heads) * self.head_dim
         o = self.num_heads * self.head_dim * H
         mlp = 3 * H * Fi
+        if self.qkv_bias:
+            qkv += (self.num_heads + 2 * self.num_kv_heads) * self.head_dim
         return L * (qkv + o + mlp + 2 * H) + V * H * (1 if self.tie_embeddings else 2) + H
 
     def flops_per_token(self, ctx: int = 0) -> float:
@@ -79,6 +82,13 @@ PRESETS = {
     "llama-small": LlamaConfig(name="llama-small", vocab_size=32000, hidden_size=1024, intermediate_size=2816,
                                num_layers=4, num_heads=8, num_kv_heads=2, head_dim=128, max_position=4096,
                                bos_token_id=1, eos_token_ids=(2,)),
+    # the same two shapes as Qwen2: a bias on the QKV projection, RoPE base 1e6, eps 1e-6
+    "qwen2-tiny": LlamaConfig(name="qwen2-tiny", vocab_size=512, hidden_size=256, intermediate_size=512,
+                              num_layers=2, num_heads=4, num_kv_heads=2, head_dim=64, max_position=2048,
+                              bos_token_id=1, eos_token_ids=(2,), qkv_bias=True, rope_theta=1e6, rms_eps=1e-6),
+    "qwen2-small": LlamaConfig(name="qwen2-small", vocab_size=32000, hidden_size=1024, intermediate_size=2816,
+                               num_layers=4, num_heads=8, num_kv_heads=2, head_dim=128, max_position=4096,
+                               bos_token_id=1, eos_token_ids=(2,), qkv_bias=True, rope_theta=1e6, rms_eps=1e-6),
 }
 
 
@@ -172,9 +182,12 @@ class LlamaLayer:
         self.down_w = mk(H, self.f) / math.sqrt(2 * cfg.num_layers)
         self.in_norm = torch.ones(H, device=device, dtype=dtype)
         self.post_norm = torch.ones(H, device=device, dtype=dtype)
+        # packed like the rows of qkv_w: q heads, k heads, v heads
+        self.qkv_b = torch.zeros((self.hq + 2 * self.hkv) * D, device=device, dtype=dtype) if cfg.qkv_bias else None
 
     def tensors(self):
-        return [self.qkv_w, self.o_w, self.gate_up_w, self.down_w, self.in_norm, self.post_norm]
+        t = [self.qkv_w, self.o_w, self.gate_up_w, self.down_w, self.in_norm, self.post_norm]
+        return t + [self.qkv_b] if self.qkv_b is not None else t
 
 
 class LlamaModel:
@@ -208,10 +221,14 @@ class LlamaModel:
         self.kv_v_scale = 1.0
 
     # ------------------------------------------------------------------ weights io
+    def _layer_names(self) -> tuple:
+        names = ("qkv_w", "o_w", "gate_up_w", "down_w", "in_norm", "post_norm")
+        return names + ("qkv_b",) if self.cfg.qkv_bias else names
+
     def state_dict(self) -> dict:
         sd = {"embed": self.embed, "final_norm": self.final_norm, "lm_head": self.lm_head}
         for i, l in enumerate(self.layers):
-            for n in ("qkv_w", "o_w", "gate_up_w", "down_w", "in_norm", "post_norm"):
+            for n in self._layer_names():
                 sd[f"layers.{i}.{n}"] = getattr(l, n)
         return sd
 
@@ -223,7 +240,7 @@ class LlamaModel:
         if not self.cfg.tie_embeddings:
             self.lm_head.copy_(sd["lm_head"])
         for i, l in enumerate(self.layers):
-            for n in ("qkv_w", "o_w", "gate_up_w", "down_w", "in_norm", "post_norm"):
+            for n in self._layer_names():
                 getattr(l, n).copy_(sd[f"layers.{i}.{n}"])
 
     # ------------------------------------------------------------------ forward
@@ -249,7 +266,7 @@ class LlamaModel:
             kc, vc = kv_caches[li]
             qkv = _linear(x, layer.qkv_w)
             ops.rope_and_cache(qkv, meta.positions, self.cos_sin, meta.slots, kc, vc, self.hq, self.hkv,
-                               k_scale=ks, v_scale=vs)
+                               k_scale=ks, v_scale=vs, bias=layer.qkv_b)
             q = qkv[:, : self.hq * D]
             nd = meta.num_decode
             if meta.num_prefill_tokens == 0:
@@ -296,7 +313,7 @@ class LlamaModel:
             [l.down_w for l in L], [l.in_norm for l in L], [l.post_norm for l in L], self.final_norm,
             self.lm_head, [kv[0] for kv in kv_caches], [kv[1] for kv in kv_caches], self.cos_sin, self.hq,
             self.hkv, self.cfg.head_dim, self.cfg.rms_eps, self.scale, self.cfg.vocab_size, self.vocab_start, pg,
-            self.kv_k_scale, self.kv_v_scale)
+            self.kv_k_scale, self.kv_v_scale, [l.qkv_b for l in L] if self.cfg.qkv_bias else None)
         self._runner = (key, runner, kv_caches)
         return runner
 

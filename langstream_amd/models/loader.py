@@ -62,38 +62,122 @@ def load_packed(path: str, device="cpu") -> Dict[str, torch.Tensor]:
 # ---------------------------------------------------------------- Llama
 
 
+HF_MODEL_TYPES = ("llama", "mistral", "qwen2")   # Llama-architecture families the engine serves
+
+
+def hf_model_type(model_dir: str) -> str:
+    """``model_type`` of a Hugging Face directory's ``config.json`` ("llama" when absent)."""
+    with open(os.path.join(model_dir, "config.json")) as f:
+        return json.load(f).get("model_type", "llama")
+
+
+def _checkpoint_names(model_dir: str) -> set:
+    """Tensor names of a directory's ``*.safetensors`` (headers only, no tensor is read)."""
+    names: set = set()
+    for f in sorted(glob.glob(os.path.join(model_dir, "*.safetensors"))):
+        from safetensors import safe_open
+        with safe_open(f, framework="pt", device="cpu") as fh:
+            names.update(fh.keys())
+    return names
+
+
+def _rope_from_hf(c: dict) -> Tuple[float, Optional[dict]]:
+    """(base, scaling) from ``rope_parameters`` (transformers 5: base and scaling fields in
+    one object) or, without it, the top-level ``rope_theta`` / ``rope_scaling``.  Scaling is
+    None or the llama3 fields; any other type raises."""
+    rp = c.get("rope_parameters")
+    if isinstance(rp, dict):
+        theta, sc = rp.get("rope_theta", c.get("rope_theta")), rp
+    else:
+        theta, sc = c.get("rope_theta"), c.get("rope_scaling")
+    kind = (sc.get("rope_type", sc.get("type")) if sc else None) or "default"
+    if kind not in ("default", "llama3"):
+        raise ValueError(f"unsupported RoPE scaling type {kind!r} (supported: default, llama3)")
+    scaling = None
+    if kind == "llama3":
+        scaling = {"rope_type": "llama3", "factor": float(sc["factor"]),
+                   "low_freq_factor": float(sc.get("low_freq_factor", 1.0)),
+                   "high_freq_factor": float(sc.get("high_freq_factor", 4.0)),
+                   "original_max_position_embeddings": int(sc.get("original_max_position_embeddings", 8192))}
+    return float(theta if theta is not None else 10000.0), scaling
+
+
 def llama_config_from_hf(model_dir: str) -> LlamaConfig:
+    """The shape of a Hugging Face ``llama`` / ``mistral`` / ``qwen2`` directory.  Anything
+    the engine would compute differently from the checkpoint's own model is refused here
+    (other model types, other RoPE scalings) or in ``convert_hf_llama`` (other tensors)."""
     with open(os.path.join(model_dir, "config.json")) as f:
         c = json.load(f)
+    mtype = c.get("model_type", "llama")
+    if mtype not in HF_MODEL_TYPES:
+        raise ValueError(f"unsupported model_type {mtype!r} (supported: {', '.join(HF_MODEL_TYPES)})")
+    theta, scaling = _rope_from_hf(c)
+    qkv_bias = mtype == "qwen2" or any(n.endswith("self_attn.q_proj.bias") for n in _checkpoint_names(model_dir))
+    max_pos = c.get("max_position_embeddings", 8192)
+    # an active sliding window: full attention equals windowed attention up to the window,
+    # so positions past it are not served
+    window = c.get("sliding_window")
+    if mtype == "qwen2" and not c.get("use_sliding_window", False):
+        window = None
+    if mtype == "llama":
+        window = None
+    if window:
+        max_pos = min(max_pos, int(window))
     eos = c.get("eos_token_id", 2)
+    eos = list(eos) if isinstance(eos, (list, tuple)) else [eos]
+    gen = os.path.join(model_dir, "generation_config.json")
+    if os.path.exists(gen):
+        with open(gen) as f:
+            ge = json.load(f).get("eos_token_id")
+        for e in (ge if isinstance(ge, list) else [ge]):
+            if e is not None and e not in eos:
+                eos.append(e)
+    eos = [e for e in eos if e is not None]
+    bos = c.get("bos_token_id")
     return LlamaConfig(
-        name=c.get("_name_or_path", "llama"), vocab_size=c["vocab_size"], hidden_size=c["hidden_size"],
+        name=c.get("_name_or_path") or mtype, vocab_size=c["vocab_size"], hidden_size=c["hidden_size"],
         intermediate_size=c["intermediate_size"], num_layers=c["num_hidden_layers"],
-        num_heads=c["num_attention_heads"], num_kv_heads=c.get("num_key_value_heads", c["num_attention_heads"]),
-        head_dim=c.get("head_dim", c["hidden_size"] // c["num_attention_heads"]),
-        rope_theta=c.get("rope_theta", 10000.0), rope_scaling=c.get("rope_scaling"),
-        rms_eps=c.get("rms_norm_eps", 1e-5), max_position=c.get("max_position_embeddings", 8192),
-        tie_embeddings=c.get("tie_word_embeddings", False), bos_token_id=c.get("bos_token_id", 1),
-        eos_token_ids=tuple(eos) if isinstance(eos, list) else (eos,))
+        num_heads=c["num_attention_heads"],
+        num_kv_heads=c.get("num_key_value_heads") or c["num_attention_heads"],
+        head_dim=c.get("head_dim") or c["hidden_size"] // c["num_attention_heads"],
+        rope_theta=theta, rope_scaling=scaling,
+        rms_eps=c.get("rms_norm_eps", 1e-5), max_position=max_pos,
+        tie_embeddings=bool(c.get("tie_word_embeddings", False)), bos_token_id=1 if bos is None else bos,
+        eos_token_ids=tuple(eos), qkv_bias=qkv_bias)
 
 
 def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = None) -> Dict[str, torch.Tensor]:
-    """HF ``LlamaForCausalLM`` names -> packed names (fused qkv / gate_up)."""
-    out = {"embed": hf["model.embed_tokens.weight"], "final_norm": hf["model.norm.weight"]}
-    out["lm_head"] = hf.get("lm_head.weight", hf["model.embed_tokens.weight"])
+    """HF ``LlamaForCausalLM`` / ``MistralForCausalLM`` / ``Qwen2ForCausalLM`` names -> packed
+    names (fused qkv / gate_up, ``q/k/v_proj.bias`` fused into ``qkv_b``).  A checkpoint is
+    loaded whole or refused: a tensor that is not consumed (``o_proj.bias``, ``q_norm``, ...)
+    raises ValueError naming it; ``rotary_emb.inv_freq`` is the only name skipped."""
+    used = set()
+
+    def take(name):
+        used.add(name)
+        return hf[name]
+
+    out = {"embed": take("model.embed_tokens.weight"), "final_norm": take("model.norm.weight")}
+    out["lm_head"] = take("lm_head.weight") if "lm_head.weight" in hf else hf["model.embed_tokens.weight"]
     i = 0
     while f"model.layers.{i}.self_attn.q_proj.weight" in hf:
         p = f"model.layers.{i}."
-        out[f"layers.{i}.qkv_w"] = torch.cat([hf[p + "self_attn.q_proj.weight"], hf[p + "self_attn.k_proj.weight"],
-                                              hf[p + "self_attn.v_proj.weight"]], 0)
-        out[f"layers.{i}.o_w"] = hf[p + "self_attn.o_proj.weight"]
-        out[f"layers.{i}.gate_up_w"] = torch.cat([hf[p + "mlp.gate_proj.weight"], hf[p + "mlp.up_proj.weight"]], 0)
-        out[f"layers.{i}.down_w"] = hf[p + "mlp.down_proj.weight"]
-        out[f"layers.{i}.in_norm"] = hf[p + "input_layernorm.weight"]
-        out[f"layers.{i}.post_norm"] = hf[p + "post_attention_layernorm.weight"]
+        qkv = [p + f"self_attn.{n}_proj" for n in "qkv"]
+        out[f"layers.{i}.qkv_w"] = torch.cat([take(n + ".weight") for n in qkv], 0)
+        if any(n + ".bias" in hf for n in qkv):
+            out[f"layers.{i}.qkv_b"] = torch.cat([take(n + ".bias") for n in qkv], 0)
+        out[f"layers.{i}.o_w"] = take(p + "self_attn.o_proj.weight")
+        out[f"layers.{i}.gate_up_w"] = torch.cat([take(p + "mlp.gate_proj.weight"), take(p + "mlp.up_proj.weight")], 0)
+        out[f"layers.{i}.down_w"] = take(p + "mlp.down_proj.weight")
+        out[f"layers.{i}.in_norm"] = take(p + "input_layernorm.weight")
+        out[f"layers.{i}.post_norm"] = take(p + "post_attention_layernorm.weight")
         i += 1
     if cfg is not None:
         assert i == cfg.num_layers, f"checkpoint has {i} layers, config {cfg.num_layers}"
+    left = sorted(n for n in hf if n not in used and not n.endswith("rotary_emb.inv_freq"))
+    if left:
+        raise ValueError(f"checkpoint tensor {left[0]!r} is not supported"
+                         + (f" (and {len(left) - 1} more)" if len(left) > 1 else ""))
     return out
 
 
@@ -112,7 +196,7 @@ def shard_llama(sd: Dict[str, torch.Tensor], cfg: LlamaConfig, rank: int, world:
     vpr = (cfg.vocab_size + world - 1) // world
     out = {}
     for k, v in sd.items():
-        if k.endswith(".qkv_w"):
+        if k.endswith((".qkv_w", ".qkv_b")):   # the bias is sliced like the rows it belongs to
             q, kk, vv = v[:Hq], v[Hq: Hq + Hkv], v[Hq + Hkv:]
             out[k] = torch.cat([q[rank * hq * D:(rank + 1) * hq * D], kk[kv0 * D:(kv0 + hkv) * D],
                                 vv[kv0 * D:(kv0 + hkv) * D]], 0)

@@ -56,7 +56,9 @@ inline bool is_letter_at(const std::string& s, size_t i) {
 // Approximation of the cl100k_base split pattern:
 //  '(?i:[sdmt]|ll|ve|re) | [^\r\n\p{L}\p{N}]?\p{L}+ | \p{N}{1,3} | ' '?[^\s\p{L}\p{N}]+[\r\n]* |
 //  \s*[\r\n] | \s+(?!\S) | \s+
-std::vector<std::pair<size_t, size_t>> pretokenize(const std::string& s) {
+// max_digits: the longest digit run of one piece -- 3 for cl100k / Llama-3 (\p{N}{1,3}), 1
+// for Qwen2, whose pattern takes digits one at a time (\p{N}).
+std::vector<std::pair<size_t, size_t>> pretokenize(const std::string& s, size_t max_digits = 3) {
   std::vector<std::pair<size_t, size_t>> out;
   const size_t n = s.size();
   size_t i = 0;
@@ -96,7 +98,7 @@ std::vector<std::pair<size_t, size_t>> pretokenize(const std::string& s) {
     }
     if (is_digit(c)) {
       size_t j = i;
-      while (j < n && j - i < 3 && is_digit((unsigned char)s[j])) ++j;
+      while (j < n && j - i < max_digits && is_digit((unsigned char)s[j])) ++j;
       out.push_back({i, j - i});
       i = j;
       continue;
@@ -164,7 +166,8 @@ class ByteBPE {
   // vocab: token bytes -> id.  merges: list of (left bytes, right bytes) in priority
   // order; empty -> tiktoken mode (priority = id/rank of the merged token).
   ByteBPE(const std::vector<std::pair<py::bytes, int>>& vocab, const std::vector<std::pair<py::bytes, py::bytes>>& merges,
-          const std::vector<std::pair<std::string, int>>& specials) {
+          const std::vector<std::pair<std::string, int>>& specials, int max_digits = 3)
+      : max_digits_((size_t)std::max(1, max_digits)) {
     for (auto& kv : vocab) {
       std::string b = kv.first;
       tok2id_[b] = kv.second;
@@ -273,7 +276,7 @@ class ByteBPE {
 
  private:
   void encode_ordinary(const std::string& text, std::vector<int>& out) {
-    for (auto& span : pretokenize(text)) {
+    for (auto& span : pretokenize(text, max_digits_)) {
       const std::string word = text.substr(span.first, span.second);
       {
         std::shared_lock<std::shared_mutex> g(cache_mu_);
@@ -335,6 +338,7 @@ class ByteBPE {
   std::vector<size_t> special_lens_;
   int byte_id_[256];
   bool tiktoken_ = true;
+  size_t max_digits_ = 3;   // longest digit run of one pre-token
   std::unordered_map<std::string, std::vector<int>> cache_;
   std::shared_mutex cache_mu_;
 };
@@ -661,7 +665,8 @@ std::vector<std::pair<size_t, size_t>> pretokenize_py(const std::string& s) { re
 void bind_tokenizer(py::module_& m) {
   py::class_<ByteBPE>(m, "ByteBPE")
       .def(py::init<const std::vector<std::pair<py::bytes, int>>&, const std::vector<std::pair<py::bytes, py::bytes>>&,
-                    const std::vector<std::pair<std::string, int>>&>())
+                    const std::vector<std::pair<std::string, int>>&, int>(),
+           py::arg("vocab"), py::arg("merges"), py::arg("specials"), py::arg("max_digits") = 3)
       .def("encode", &ByteBPE::encode, py::arg("text"), py::arg("allow_special") = true,
            py::call_guard<py::gil_scoped_release>())
       .def("encode_batch", &ByteBPE::encode_batch, py::arg("texts"), py::arg("allow_special") = true,

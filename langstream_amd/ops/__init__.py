@@ -236,12 +236,13 @@ def bias_gelu_(x: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
 
 # ---------------------------------------------------------------- rope / kv cache
 def rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq: int, Hkv: int, apply_rope: bool = True,
-                   k_scale: float = 1.0, v_scale: float = 1.0):
-    """k_scale / v_scale: the scales of an fp8 cache (ignored by bf16 caches)."""
+                   k_scale: float = 1.0, v_scale: float = 1.0, bias: Optional[torch.Tensor] = None):
+    """k_scale / v_scale: the scales of an fp8 cache (ignored by bf16 caches).  bias: the
+    QKV projection's bias [(Hq + 2 Hkv) D], added before the rotation (q, k and v)."""
     if _gpu(qkv):
-        hip().rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope, k_scale, v_scale)
+        hip().rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope, k_scale, v_scale, bias)
     else:
-        ref.rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope, k_scale, v_scale)
+        ref.rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope, k_scale, v_scale, bias)
 
 
 # ---------------------------------------------------------------- attention

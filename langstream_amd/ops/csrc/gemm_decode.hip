@@ -799,9 +799,12 @@ void decode_gemm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspac
 // form: the fused-RoPE attention measured 91.6 vs 80.4 us at B = 256, ctx 410,
 // profiles/decode_attn_rope_isolated_r3.log).
 // F8: e4m3 caches; K as two 4-byte stores, V as 1-byte stores at an 8-byte stride.
-template <int D, bool F8>
+// BIAS: the projection's bias (bf16 [(Hq + 2 Hkv) D], q / k / v heads in the packed order)
+// is added to the f32 sums before the rotation, for v heads too.
+template <int D, bool F8, bool BIAS>
 __global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(const float* __restrict__ part, int S, int M, int N,
-                                                                 bf16* __restrict__ out, int64_t ldo, KvWrite kw) {
+                                                                 bf16* __restrict__ out, int64_t ldo, KvWrite kw,
+                                                                 const bf16* __restrict__ bias) {
   constexpr int HALF = D / 2, G4 = HALF / 4;
   const int H = kw.Hq + 2 * kw.Hkv;
   const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -814,6 +817,11 @@ __global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(const float* __
   const int64_t e0 = (int64_t)m * N + (int64_t)hd * D + 4 * c;
   constexpr int SMAX = 8;
   float4 lo[SMAX], hi[SMAX];
+  bf16x4 ba, bb;   // BIAS: fetched with the slabs, not after their sums
+  if constexpr (BIAS) {
+    ba = *reinterpret_cast<const bf16x4*>(bias + hd * D + 4 * c);
+    bb = *reinterpret_cast<const bf16x4*>(bias + hd * D + HALF + 4 * c);
+  }
 #pragma unroll
   for (int s = 0; s < SMAX; ++s)
     if (s < S) {
@@ -833,6 +841,13 @@ __global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(const float* __
     a[0] += x.x; a[1] += x.y; a[2] += x.z; a[3] += x.w;
     b[0] += y.x; b[1] += y.y; b[2] += y.z; b[3] += y.w;
   }
+  if constexpr (BIAS) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      a[j] += (float)ba[j];
+      b[j] += (float)bb[j];
+    }
+  }
   qkv_finish<D, F8>(kw, f32x4{a[0], a[1], a[2], a[3]}, f32x4{b[0], b[1], b[2], b[3]}, 1.f, m, hd, c, out, ldo);
 }
 
@@ -840,7 +855,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(const float* __
 // written to the paged cache (the same contract as decode_gemm + rope_and_cache).
 void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor pos,
                           at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, int64_t Hq,
-                          int64_t Hkv, double k_scale, double v_scale) {
+                          int64_t Hkv, double k_scale, double v_scale, c10::optional<at::Tensor> bias) {
   check_xw(x, w);
   const int M = (int)x.size(0), K = (int)x.size(1), N = (int)w.size(0);
   bool f8;
@@ -849,13 +864,14 @@ void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor
   const int D = (int)k_cache.size(3);
   TORCH_CHECK(N == (Hq + 2 * Hkv) * D && N % 128 == 0, "decode_gemm_qkv_rope: qkv width");
   TORCH_CHECK(qkv.scalar_type() == at::kBFloat16 && qkv.size(0) == M && qkv.size(1) == N && qkv.stride(1) == 1);
+  const bf16* bp = qkv_bias_ptr("decode_gemm_qkv_rope", bias, qkv, N);
   const int bn = pick_bn(N), tiles = N / bn;
   // at most 4 K slices: the fused reduction reads every slab once more (qkv at M = 256:
   // 27.5 us with 4 slices vs 28.1 with the 5 pick_split chooses, profiles/dgemm_bench_r3b.log)
   const int S = std::min(4, pick_split(tiles, K, 4));
   if (S == 1 || D != 128) {
     decode_gemm(qkv, x, w, workspace, c10::nullopt, c10::nullopt, 1e-5, 0, 0);
-    rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, true, k_scale, v_scale);
+    rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, true, k_scale, v_scale, bias);
     return;
   }
   TORCH_CHECK(workspace.scalar_type() == at::kFloat && workspace.numel() >= (int64_t)S * M * N,
@@ -867,11 +883,14 @@ void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor
   else
     dgemm_launch<128, EPI_PARTIAL>(S, tiles, st, x, w, M, N, K, nullptr, 0, part, 0, nullptr, nullptr, nullptr);
   const int64_t threads = (int64_t)M * (Hq + 2 * Hkv) * (D / 8);
-#define LAUNCH_RR(FF)                                                                     \
-  splitk_reduce_rope_kernel<128, FF><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>( \
-      part, S, M, N, (bf16*)qkv.data_ptr(), qkv.stride(0), kw)
-  if (f8) LAUNCH_RR(true); else LAUNCH_RR(false);
+#define LAUNCH_RB(FF, BB)                                                                     \
+  splitk_reduce_rope_kernel<128, FF, BB><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>( \
+      part, S, M, N, (bf16*)qkv.data_ptr(), qkv.stride(0), kw, bp)
+#define LAUNCH_RR(FF) \
+  if (bp) LAUNCH_RB(FF, true); else LAUNCH_RB(FF, false)
+  if (f8) { LAUNCH_RR(true); } else { LAUNCH_RR(false); }
 #undef LAUNCH_RR
+#undef LAUNCH_RB
 }
 
 // f32 OUTPUT (the LM head: logits the sampler reads in f32): out[M, N] f32 contiguous =

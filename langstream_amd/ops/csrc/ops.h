@@ -49,6 +49,22 @@ inline float kv_inv_scale(double scale) {
   return 1.0f / (float)scale;
 }
 
+// ---------------------------------------------------------------------------- qkv bias
+// The optional bias of a fused QKV projection (Qwen2): bf16 [(Hq + 2 Hkv) D] in the packed
+// order q heads, k heads, v heads, added in f32 before the rotation.  Returns its data
+// pointer, nullptr without a bias; `who` names the op in the messages.
+inline const bf16* qkv_bias_ptr(const char* who, const c10::optional<at::Tensor>& bias, const at::Tensor& qkv,
+                                int64_t width) {
+  if (!bias.has_value()) return nullptr;
+  const at::Tensor& b = *bias;
+  TORCH_CHECK(b.is_cuda() && b.device() == qkv.device(), who, ": bias must be on the device of qkv");
+  TORCH_CHECK(b.scalar_type() == at::kBFloat16, who, ": bias must be bf16");
+  TORCH_CHECK(b.is_contiguous(), who, ": bias must be contiguous");
+  TORCH_CHECK(b.numel() == width, who, ": bias has ", b.numel(), " elements, (Hq + 2 Hkv) D = ", width);
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(b.data_ptr()) & 15) == 0, who, ": bias must be 16-byte aligned");
+  return reinterpret_cast<const bf16*>(b.data_ptr());
+}
+
 // ---------------------------------------------------------------------------- norm.hip
 void rmsnorm(at::Tensor out, at::Tensor x, at::Tensor w, double eps);
 void fused_add_rmsnorm(at::Tensor x, at::Tensor residual, at::Tensor w, double eps);
@@ -63,7 +79,8 @@ void bias_gelu(at::Tensor x, c10::optional<at::Tensor> bias);
 
 // ---------------------------------------------------------------------------- rope.hip
 void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache,
-                    at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope, double k_scale, double v_scale);
+                    at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope, double k_scale, double v_scale,
+                    c10::optional<at::Tensor> bias);
 
 // ---------------------------------------------------------------- attention_decode.hip
 void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
@@ -176,7 +193,7 @@ void decode_gemm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspac
                  c10::optional<at::Tensor> norm_w, double eps, int64_t bn_force, int64_t splits_force);
 void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor pos,
                           at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, int64_t Hq,
-                          int64_t Hkv, double k_scale, double v_scale);
+                          int64_t Hkv, double k_scale, double v_scale, c10::optional<at::Tensor> bias);
 bool decode_gemm_f32_supported(const at::Tensor& w, int64_t M);
 void decode_gemm_f32(at::Tensor out, at::Tensor x, at::Tensor w, int64_t bn_force);
 void decode_gemm_silu(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor tickets,

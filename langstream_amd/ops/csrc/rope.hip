@@ -33,9 +33,14 @@ constexpr int HG = 8;    // heads per rotate workgroup
 
 // F8: e4m3 caches (kv_write.h): K as one 8-byte store per 8 rotated values, V as 1-byte
 // stores at an 8-byte stride.
-template <int D, int TOK, bool F8>
+// BIAS: a bf16 bias [(Hq + 2 Hkv) D] (q, k, v heads in the packed order: a QKV projection
+// with bias, Qwen2) is added in f32 before the rotation, one rounding as without it.  V
+// gets it too, so the V branch then writes bf16(v + b) back into the row as well as into
+// the cache -- the cache holds the bf16 value of the row (kv_write.h) for all three parts
+// -- and does so for tokens that are not cached.
+template <int D, int TOK, bool F8, bool BIAS>
 __global__ void __launch_bounds__(256) rope_cache_kernel(bf16* __restrict__ qkv, KvWrite kw, int64_t T,
-                                                         int apply_rope) {
+                                                         int apply_rope, const bf16* __restrict__ bias) {
   constexpr int HALF = D / 2;
   constexpr int VPH = HALF / 8;  // 16-B vectors per half head
   const int Hq = kw.Hq, Hkv = kw.Hkv;
@@ -60,6 +65,16 @@ __global__ void __launch_bounds__(256) rope_cache_kernel(bf16* __restrict__ qkv,
       float a[8], b[8];
       unpack8(ld16(base + c * 8), a);
       unpack8(ld16(base + HALF + c * 8), b);
+      if constexpr (BIAS) {
+        float ba[8], bb[8];
+        unpack8(ld16(bias + h * D + c * 8), ba);
+        unpack8(ld16(bias + h * D + HALF + c * 8), bb);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          a[j] += ba[j];
+          b[j] += bb[j];
+        }
+      }
       if (apply_rope) {
         float co[8], si[8];
         kv_load_cos_sin<8>(kv_cos_sin_row(kw, t, D), D, c * 8, co, si);
@@ -83,16 +98,27 @@ __global__ void __launch_bounds__(256) rope_cache_kernel(bf16* __restrict__ qkv,
   if (tl >= ntok) return;
   const int64_t t = t0 + tl;
   KvSlot s;
-  if (!kv_slot(kw, t, s)) return;
-  const bf16* src = qkv + t * row_elems + (Hq + Hkv + hv) * D;
-  for (int d = dr; d < D; d += 256 / TOK) kv_store_v<F8, 1>(kw, s, hv, D, d, src[d]);
+  if constexpr (BIAS) {
+    const bool cached = kv_slot(kw, t, s);
+    bf16* row = qkv + t * row_elems + (Hq + Hkv + hv) * D;
+    const bf16* bv = bias + (Hq + Hkv + hv) * D;
+    for (int d = dr; d < D; d += 256 / TOK) {
+      const bf16 v = (bf16)((float)row[d] + (float)bv[d]);
+      row[d] = v;
+      if (cached) kv_store_v<F8, 1>(kw, s, hv, D, d, v);
+    }
+  } else {
+    if (!kv_slot(kw, t, s)) return;
+    const bf16* src = qkv + t * row_elems + (Hq + Hkv + hv) * D;
+    for (int d = dr; d < D; d += 256 / TOK) kv_store_v<F8, 1>(kw, s, hv, D, d, src[d]);
+  }
 }
 
 }  // namespace
 
 void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache,
                     at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope, double k_scale,
-                    double v_scale) {
+                    double v_scale, c10::optional<at::Tensor> bias) {
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.is_contiguous());
   TORCH_CHECK(k_cache.dim() == 4, "k_cache [NB, Hkv, BS, D], v_cache [NB, Hkv, BS/8, D, 8]");
   const int D = k_cache.size(3);
@@ -102,19 +128,23 @@ void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tens
   const KvWrite kw = make_kv_write("rope_and_cache", pos, cos_sin, slots, k_cache, v_cache, T, Hq, Hkv, true,
                                    k_scale, v_scale, &f8);
   TORCH_CHECK(pos.numel() == T && slots.numel() == T);
+  const bf16* bp = qkv_bias_ptr("rope_and_cache", bias, qkv, (Hq + 2 * Hkv) * D);
   if (T == 0) return;
   auto stream = at::hip::getCurrentHIPStream();
   const int nq = (int)((Hq + HG - 1) / HG), nk = (int)((Hkv + HG - 1) / HG);
   const bool small = T <= SMALL_T;
   const int tok = small ? TOK_SMALL : TOK_LARGE;
   dim3 grid((unsigned)((T + tok - 1) / tok), nq + nk + (int)Hkv);
+#define LAUNCH_B(DD, TT, FF, BB) \
+  rope_cache_kernel<DD, TT, FF, BB><<<grid, 256, 0, stream>>>((bf16*)qkv.data_ptr(), kw, T, apply_rope ? 1 : 0, bp)
 #define LAUNCH_F(DD, TT, FF) \
-  rope_cache_kernel<DD, TT, FF><<<grid, 256, 0, stream>>>((bf16*)qkv.data_ptr(), kw, T, apply_rope ? 1 : 0)
+  if (bp) LAUNCH_B(DD, TT, FF, true); else LAUNCH_B(DD, TT, FF, false)
 #define LAUNCH(DD, TT) \
-  if (f8) LAUNCH_F(DD, TT, true); else LAUNCH_F(DD, TT, false)
+  if (f8) { LAUNCH_F(DD, TT, true); } else { LAUNCH_F(DD, TT, false); }
   if (D == 128) { if (small) { LAUNCH(128, TOK_SMALL); } else { LAUNCH(128, TOK_LARGE); } }
   else if (D == 64) { if (small) { LAUNCH(64, TOK_SMALL); } else { LAUNCH(64, TOK_LARGE); } }
   else TORCH_CHECK(false, "unsupported head dim ", D);
 #undef LAUNCH
 #undef LAUNCH_F
+#undef LAUNCH_B
 }

@@ -95,7 +95,8 @@ class LlamaRunner {
               std::vector<at::Tensor> post_norm, at::Tensor final_norm, at::Tensor lm_head,
               std::vector<at::Tensor> k_caches, std::vector<at::Tensor> v_caches, at::Tensor cos_sin, int64_t hq,
               int64_t hkv, int64_t head_dim, double eps, double scale, int64_t vocab_size, int64_t vocab_start,
-              py::object process_group, double k_scale = 1.0, double v_scale = 1.0)
+              py::object process_group, double k_scale = 1.0, double v_scale = 1.0,
+              c10::optional<std::vector<at::Tensor>> qkv_b = c10::nullopt)
       : embed_(embed), qkv_w_(qkv_w), o_w_(o_w), gate_up_w_(gate_up_w), down_w_(down_w), in_norm_(in_norm),
         post_norm_(post_norm), final_norm_(final_norm), lm_head_(lm_head), kc_(k_caches), vc_(v_caches),
         cos_sin_(cos_sin), hq_(hq), hkv_(hkv), d_(head_dim), eps_(eps), scale_(scale), vocab_(vocab_size),
@@ -109,6 +110,14 @@ class LlamaRunner {
     for (size_t l = 1; l < L; ++l)
       TORCH_CHECK(kv_is_fp8(kc_[l], vc_[l], "LlamaRunner") == f8_, "LlamaRunner: KV caches of one dtype");
     TORCH_CHECK(k_scale > 0.0 && v_scale > 0.0, "LlamaRunner: KV cache scales must be positive");
+    // a bias on the fused QKV projection (Qwen2): one bf16 [(Hq + 2 Hkv) D] per layer,
+    // added by rope_and_cache / decode_gemm_qkv_rope; the mode follows the list
+    if (qkv_b.has_value() && !qkv_b->empty()) {
+      qkv_b_ = *qkv_b;
+      TORCH_CHECK(qkv_b_.size() == L, "LlamaRunner: one qkv bias per layer");
+      for (size_t l = 0; l < L; ++l) qkv_bias_ptr("LlamaRunner", qkv_b_[l], qkv_w_[l], qkv_w_[l].size(0));
+      bias_ = true;
+    }
     if (!process_group.is_none()) pg_ = py::cast<c10::intrusive_ptr<::c10d::ProcessGroup>>(process_group);
     // LS_ONESHOT_AR=1: decode-sized all-reduces (<= LS_ONESHOT_AR_MAX elements, default
     // 256 x 8192) through the one-shot IPC kernel (allreduce.hip) instead of RCCL.  Both
@@ -137,7 +146,7 @@ class LlamaRunner {
       }
       // the norm-deferred layer (forward_dgemm): combine-path splits must exist for qkv /
       // o / down, the head dim must be 128 (one head per 128-column tile)
-      bool fz = !pg_ && !f8_ && head_dim == 128 && fused_env();
+      bool fz = !pg_ && !f8_ && !bias_ && head_dim == 128 && fused_env();
       const int64_t H = embed_.size(1);
       for (size_t l = 0; l < L && fz; ++l) {
         const at::Tensor* ws[3] = {&qkv_w_[l], &o_w_[l], &down_w_[l]};
@@ -312,13 +321,14 @@ class LlamaRunner {
     // roped: RoPE + the K/V cache write already done by the qkv GEMM / GEMV
     auto attend = [&](int64_t l, const at::Tensor& qkv, bool roped) {
       at::Tensor attn = at::empty({T, hq_ * d_}, qkv.options());
-      if (!roped && decode_only && !f8_ && rope_fused()) {
+      if (!roped && decode_only && !f8_ && !bias_ && rope_fused()) {
         // decode-only step: RoPE + K/V cache write inside the attention kernel
         paged_decode_attention_rope(attn, qkv, pos, cos_sin_, slots, kc_[l], vc_[l], d_bt, d_ctx, scale_, nsplit,
                                     bps, ws);
         return attn;
       }
-      if (!roped) rope_and_cache(qkv, pos, cos_sin_, slots, kc_[l], vc_[l], hq_, hkv_, true, k_scale_, v_scale_);
+      if (!roped)
+        rope_and_cache(qkv, pos, cos_sin_, slots, kc_[l], vc_[l], hq_, hkv_, true, k_scale_, v_scale_, bias(l));
       at::Tensor q = qkv.narrow(1, 0, hq_ * d_);
       if (num_decode > 0)
         paged_decode_attention(attn.narrow(0, 0, num_decode), q.narrow(0, 0, num_decode), kc_[l], vc_[l], d_bt,
@@ -333,8 +343,10 @@ class LlamaRunner {
     // from the L2-resident activations -- no separate norm kernels or hand-offs.  (A
     // last-block add+norm epilogue with an agent-scope ticket measured slower: 3.72 vs
     // 3.48 ms per batch-1 step, the serial tail outweighs the launch it saves.)
-    // (fp8 KV caches: the GEMV's qkv epilogue writes bf16 K/V, so the un-fused GEMVs below)
-    bool fused = gv && !pg_ && !f8_;
+    // (fp8 KV caches: the GEMV's qkv epilogue writes bf16 K/V, so the un-fused GEMVs below;
+    // a qkv bias: gemv_qkv and the RoPE-in-attention kernel do not add one, so the plain
+    // GEMV followed by rope_and_cache with the bias)
+    bool fused = gv && !pg_ && !f8_ && !bias_;
     for (int64_t l = 0; l < L && fused; ++l)
       fused = gemv_supported(qkv_w_[l], false) && gemv_supported(o_w_[l], false) &&
               gemv_supported(gate_up_w_[l], true) && gemv_supported(down_w_[l], false);
@@ -385,7 +397,7 @@ class LlamaRunner {
         qkv = at::empty({T, qkv_w_[l].size(0)}, x.options());
         if (decode_only && qkv_rope_fused()) {
           decode_gemm_qkv_rope(qkv, x, qkv_w_[l], dg_ws_, pos, cos_sin_, slots, kc_[l], vc_[l], hq_, hkv_, k_scale_,
-                               v_scale_);
+                               v_scale_, bias(l));
           roped = true;
         } else {
           decode_gemm(qkv, x, qkv_w_[l], dg_ws_, c10::nullopt, c10::nullopt, eps_, 0, 0);
@@ -510,7 +522,7 @@ class LlamaRunner {
     return on;
   }
   bool fused_ready(int64_t T) const {
-    return cnt_qkv_.defined() && dgemm_enabled() && T >= std::max(dgemm_min_t(), fused_min_t()) &&
+    return !bias_ && cnt_qkv_.defined() && dgemm_enabled() && T >= std::max(dgemm_min_t(), fused_min_t()) &&
            T <= kDgemmMaxM;
   }
 
@@ -703,6 +715,11 @@ class LlamaRunner {
   int64_t vocab_, vocab_start_;
   double k_scale_, v_scale_;   // fp8 KV cache scales (unused with bf16 caches)
   bool f8_ = false;            // the KV caches are float8_e4m3fn
+  std::vector<at::Tensor> qkv_b_;   // per-layer bias of the QKV projection, empty without
+  bool bias_ = false;
+  c10::optional<at::Tensor> bias(int64_t l) const {
+    return bias_ ? c10::optional<at::Tensor>(qkv_b_[l]) : c10::nullopt;
+  }
   c10::intrusive_ptr<::c10d::ProcessGroup> pg_;
 };
 
@@ -1324,12 +1341,14 @@ void bind_runners(py::module_& m) {
       .def(py::init<at::Tensor, std::vector<at::Tensor>, std::vector<at::Tensor>, std::vector<at::Tensor>,
                     std::vector<at::Tensor>, std::vector<at::Tensor>, std::vector<at::Tensor>, at::Tensor, at::Tensor,
                     std::vector<at::Tensor>, std::vector<at::Tensor>, at::Tensor, int64_t, int64_t, int64_t, double,
-                    double, int64_t, int64_t, py::object, double, double>(),
+                    double, int64_t, int64_t, py::object, double, double,
+                    c10::optional<std::vector<at::Tensor>>>(),
            py::arg("embed"), py::arg("qkv_w"), py::arg("o_w"), py::arg("gate_up_w"), py::arg("down_w"),
            py::arg("in_norm"), py::arg("post_norm"), py::arg("final_norm"), py::arg("lm_head"), py::arg("k_caches"),
            py::arg("v_caches"), py::arg("cos_sin"), py::arg("hq"), py::arg("hkv"), py::arg("head_dim"),
            py::arg("eps"), py::arg("scale"), py::arg("vocab_size"), py::arg("vocab_start"),
-           py::arg("process_group"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0)
+           py::arg("process_group"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0,
+           py::arg("qkv_b") = py::none())
       .def("forward", &LlamaRunner::forward, py::call_guard<py::gil_scoped_release>());
   py::class_<BertRunner>(m, "BertRunner")
       .def(py::init<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<std::vector<at::Tensor>>,

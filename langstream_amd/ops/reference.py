@@ -138,14 +138,21 @@ def apply_rope(x, pos, cos_sin):
 
 
 def rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope_flag=True, k_scale=1.0,
-                   v_scale=1.0):
+                   v_scale=1.0, bias=None):
+    """bias: [(Hq + 2 Hkv) D] in the packed order q, k, v heads (a QKV projection with bias),
+    added in f32 before the rotation, to v heads too; the row is rounded once."""
     assert k_cache.dtype == v_cache.dtype, "K and V caches of one dtype"
     f8 = is_fp8(k_cache)
     T = qkv.shape[0]
     D = k_cache.shape[3]
     BS = k_cache.shape[2]
     v = qkv.view(T, Hq + 2 * Hkv, D)
-    if apply_rope_flag:
+    if bias is not None:
+        vf = v.float() + bias.float().view(Hq + 2 * Hkv, D)
+        if apply_rope_flag:
+            vf[:, : Hq + Hkv] = apply_rope(vf[:, : Hq + Hkv], pos, cos_sin)
+        v.copy_(vf)
+    elif apply_rope_flag:
         v[:, : Hq + Hkv] = apply_rope(v[:, : Hq + Hkv], pos, cos_sin)
     for t in range(T):
         s = int(slots[t])

@@ -18,7 +18,11 @@ Configuration (``local-gpu-configuration`` resource):
   max-model-len (4096), max-prefill-tokens (16384), kv-fraction (0.55), use-graphs (true),
   kv-cache-dtype (auto | bf16 | fp8; unset: the LS_KV_CACHE_DTYPE environment variable, else auto),
   kv-k-scale / kv-v-scale (1.0; the two scalars of an fp8 KV cache),
-  weights-path / embeddings-weights-path (optional safetensors with our packed layout).
+  weights-path / embeddings-weights-path (optional safetensors with our packed layout),
+  model-path (a Hugging Face directory: config.json, *.safetensors, tokenizer.json; llama /
+  mistral / qwen2; the model's shape, weights and tokenizer come from it and it serves every
+  local completion, like force-chat-model), chat-template (llama3 | chatml; default chatml
+  for a qwen2 model-path, llama3 otherwise).
 """
 from __future__ import annotations
 
@@ -113,15 +117,28 @@ class ServiceRegistry:
         from .models.llama import LlamaModel, PRESETS
         from .tokenizers import BPETokenizer
         c = self._local_cfg(cfg)
-        name = _norm_model(c.get("force-chat-model") or model) or _norm_model(c.get("chat-model")) or "llama-3-8b"
-        if name not in PRESETS:
-            name = _norm_model(c.get("chat-model")) or "llama-3-8b"
+        model_path = c.get("model-path")
+        template = c.get("chat-template")
+        if template is not None and template not in ("llama3", "chatml"):
+            raise ValueError(f"chat-template {template!r}: expected llama3 or chatml")
+        if model_path:
+            # a Hugging Face directory: one engine per directory, whatever model name the agent asks for
+            name = "path:" + os.path.abspath(model_path)
+        else:
+            name = _norm_model(c.get("force-chat-model") or model) or _norm_model(c.get("chat-model")) or "llama-3-8b"
+            if name not in PRESETS:
+                name = _norm_model(c.get("chat-model")) or "llama-3-8b"
         with self._lock:
             eng = self._llms.get(name)
             if eng is not None:
                 return eng
             device = c.get("device") or default_device()
-            mcfg = PRESETS[name]
+            if model_path:
+                from .models.loader import hf_model_type, llama_config_from_hf
+                mcfg = llama_config_from_hf(model_path)
+                template = template or ("chatml" if hf_model_type(model_path) == "qwen2" else "llama3")
+            else:
+                mcfg = PRESETS[name]
             dtype = torch.bfloat16 if device.startswith("cuda") else torch.float32
             if self.tp is not None and self.tp.world > 1:
                 # bring-up self-check of the TP collectives before any weight is loaded: a
@@ -135,14 +152,16 @@ class ServiceRegistry:
                     c["use-graphs"] = "false"
             log.info("starting LLM engine %s on %s", name, device)
             model_ = LlamaModel(mcfg, device=device, dtype=dtype, tp=self.tp)
-            if c.get("weights-path"):
+            if model_path or c.get("weights-path"):
                 from .models.loader import load_packed, shard_llama
-                sd = load_packed(c["weights-path"], device)
+                sd = load_packed(model_path or c["weights-path"], device)
                 if self.tp is not None and self.tp.world > 1:
                     sd = shard_llama(sd, mcfg, self.tp.rank, self.tp.world)
                 model_.load_state_dict(sd)
-            tok = BPETokenizer.synthetic(mcfg.vocab_size) if not c.get("tokenizer-path") else (
-                BPETokenizer.from_hf_json(c["tokenizer-path"]))
+            tok_path = c.get("tokenizer-path")
+            if not tok_path and model_path and os.path.exists(os.path.join(model_path, "tokenizer.json")):
+                tok_path = os.path.join(model_path, "tokenizer.json")
+            tok = BPETokenizer.from_hf_json(tok_path) if tok_path else BPETokenizer.synthetic(mcfg.vocab_size)
             eng = LLMEngine(model_, tok, max_model_len=int(c.get("max-model-len", 4096)),
                             max_batch=int(c.get("max-batch", 256)),
                             max_prefill_tokens=int(c.get("max-prefill-tokens", 16384)),
@@ -152,6 +171,7 @@ class ServiceRegistry:
                             kv_cache_dtype=str(c.get("kv-cache-dtype") or os.environ.get("LS_KV_CACHE_DTYPE")
                                                or "auto"),
                             kv_k_scale=float(c.get("kv-k-scale", 1.0)), kv_v_scale=float(c.get("kv-v-scale", 1.0)))
+            eng.chat_template = template or "llama3"
             if eng.use_graphs and str(c.get("capture-graphs", "true")).lower() == "true":
                 eng.capture_graphs()   # TP: every rank captures in lock-step
             if self.tp is None or self.tp.rank == 0:

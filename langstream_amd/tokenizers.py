@@ -64,9 +64,12 @@ def builtin_corpus(n_sentences: int = 4000, seed: int = 7) -> List[str]:
 
 class BPETokenizer:
     def __init__(self, vocab: dict, merges: Sequence = (), specials: Optional[dict] = None,
-                 bos: Optional[str] = None, eos: Sequence[str] = ()):
+                 bos: Optional[str] = None, eos: Sequence[str] = (), max_digits: int = 3):
+        """max_digits: the longest digit run the pre-tokeniser keeps in one piece (3: the
+        cl100k / Llama-3 rule; 1: Qwen2)."""
         self.specials = dict(specials or {})
-        self._tok = lib().ByteBPE(list(vocab.items()), list(merges), list(self.specials.items()))
+        self.max_digits = max_digits
+        self._tok = lib().ByteBPE(list(vocab.items()), list(merges), list(self.specials.items()), max_digits)
         self.vocab_size = max([len(vocab)] + [i + 1 for i in self.specials.values()])
         self.bos_id = self.specials.get(bos) if bos else None
         self.eos_ids = [self.specials[e] for e in eos if e in self.specials]
@@ -92,7 +95,7 @@ class BPETokenizer:
             a, b = (m.split(" ", 1) if isinstance(m, str) else m)
             merges.append((to_b(a), to_b(b)))
         specials = {t["content"]: t["id"] for t in spec.get("added_tokens", [])}
-        return BPETokenizer(vocab, merges, specials)
+        return BPETokenizer(vocab, merges, specials, max_digits=_split_max_digits(spec.get("pre_tokenizer")))
 
     @staticmethod
     def from_tiktoken(path: str, specials: Optional[dict] = None) -> "BPETokenizer":
@@ -126,6 +129,26 @@ class BPETokenizer:
 
     def token_to_id(self, t: str) -> int:
         return self._tok.token_to_id(t)
+
+
+def _split_max_digits(pre: Optional[dict]) -> int:
+    """1 when the ``Split`` pattern of a tokenizer.json ``pre_tokenizer`` (looked for inside a
+    ``Sequence`` too) takes digits one at a time -- ``\\p{N}`` not followed by ``{1,3}``, Qwen2's
+    pattern -- else 3, the cl100k / Llama-3 rule."""
+    import re
+    if not pre:
+        return 3
+    for p in (pre.get("pretokenizers") or []) if pre.get("type") == "Sequence" else [pre]:
+        if p.get("type") == "Sequence":
+            if _split_max_digits(p) == 1:
+                return 1
+            continue
+        pat = p.get("pattern") if p.get("type") == "Split" else None
+        rx = (pat.get("Regex") or pat.get("String") or "") if isinstance(pat, dict) else ""
+        # \p{N} outside the character classes, with no {1,3} after it
+        if re.search(r"\\p\{N\}(?!\{1,3\})", re.sub(r"\[[^\]]*\]", "", rx)):
+            return 1
+    return 3
 
 
 def _unicode_to_bytes() -> dict:

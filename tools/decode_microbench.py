@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--ctx", type=int, default=512)
     ap.add_argument("--blas", default="", help="'rocblas' or 'hipblaslt' (torch preferred BLAS library)")
+    ap.add_argument("--qkv-bias", action="store_true",
+                    help="also time the two kernels that add a QKV-projection bias (Qwen2), with it and without")
     a = ap.parse_args()
     if a.blas:
         torch.backends.cuda.preferred_blas_library(a.blas)
@@ -73,6 +75,24 @@ def main():
     cs = torch.randn(8192, D, device=dev, dtype=torch.float32)
     rec("rope_and_cache", timeit(lambda: ops.hip().rope_and_cache(qkv, pos, cs, slots, kc, vc, Hq, Hkv, True)),
         B * (Hq + 2 * Hkv) * D * 2 * 2)
+    extra = []   # --qkv-bias: lines next to the layer's own ops, not part of its sum
+    if a.qkv_bias:
+        N = (Hq + 2 * Hkv) * D
+        bias = torch.randn(N, device=dev, dtype=bf)
+
+        def rec_extra(name, us, bytes_):
+            extra.append({"op": name, "us": round(us, 2), "GBps": round(bytes_ / us / 1e3, 1)})
+
+        rec_extra("rope_and_cache_bias",
+                  timeit(lambda: ops.hip().rope_and_cache(qkv, pos, cs, slots, kc, vc, Hq, Hkv, True, 1.0, 1.0, bias)),
+                  B * N * 2 * 2)
+        if B <= 256:
+            wq = torch.randn(N, H, device=dev, dtype=bf) * 0.02
+            wsp = torch.empty(ops.hip().decode_gemm_workspace(B, N, H, False) // 4 + 4 * B * N, device=dev)
+            for name, b in (("qkv_gemm_rope", None), ("qkv_gemm_rope_bias", bias)):
+                rec_extra(name, timeit(lambda: ops.hip().decode_gemm_qkv_rope(qkv, x, wq, wsp, pos, cs, slots, kc, vc,
+                                                                              Hq, Hkv, 1.0, 1.0, b)),
+                          N * H * 2 + B * (N + H) * 2)
     nsplit, bps = ops.decode_splits(64)
     ws = torch.empty(B * Hq * nsplit * (D + 2), device=dev, dtype=torch.float32)
     q = qkv[:, : Hq * D]
@@ -81,7 +101,7 @@ def main():
                                                                             min(bps, nb), ws)),
         B * ctx * Hkv * D * 2 * 2)
     per_layer = sum(r_["us"] for r_ in res)
-    for r_ in res:
+    for r_ in res + extra:
         print(json.dumps(r_))
     print(json.dumps({"per_layer_us": round(per_layer, 1), "per_step_ms_est": round(per_layer * L / 1000, 2),
                       "batch": B, "ctx": ctx}))

@@ -22,8 +22,13 @@ def sync():
 
 def bench_llm(args):
     cfg = PRESETS[args.model]
+    if args.qkv_bias:   # the same shape with a bias on the QKV projection (Qwen2)
+        import dataclasses
+        cfg = dataclasses.replace(cfg, name=cfg.name + "+qkv-bias", qkv_bias=True)
     t0 = time.time()
     model = LlamaModel(cfg, device="cuda")
+    for layer in model.layers if args.qkv_bias else ():
+        layer.qkv_b.normal_(0.0, 0.5)
     sync()
     print(json.dumps({"event": "model_init", "s": round(time.time() - t0, 2)}), flush=True)
     eng = LLMEngine(model, None, max_model_len=args.max_len, max_batch=args.batch, max_prefill_tokens=args.prefill_chunk,
@@ -52,7 +57,7 @@ def bench_llm(args):
     t2 = time.time()
     ntok = sum(len(r.output_ids) for r in reqs)
     print(json.dumps({
-        "test": "llm", "model": args.model, "batch": args.batch, "prompt": args.prompt, "gen": args.gen,
+        "test": "llm", "model": cfg.name, "batch": args.batch, "prompt": args.prompt, "gen": args.gen,
         "prefill_s": round(t1 - t0, 4), "prefill_tok_s": round(args.batch * args.prompt / (t1 - t0), 1),
         "decode_s": round(t2 - t1, 4), "decode_tok_s": round((ntok - args.batch) / (t2 - t1), 1),
         "ms_per_decode_step": round(1000 * (t2 - t1) / max(1, args.gen - 1), 3),
@@ -180,6 +185,8 @@ if __name__ == "__main__":
     ap.add_argument("--prefill-chunk", type=int, default=16384)
     ap.add_argument("--kv-dtype", choices=("auto", "bf16", "fp8"), default="auto",
                     help="KV cache element type of the LLM engine (LLMEngine kv_cache_dtype)")
+    ap.add_argument("--qkv-bias", action="store_true",
+                    help="LLM: the model's shape with a random bias on the QKV projection (LlamaConfig.qkv_bias)")
     ap.add_argument("--texts", type=int, default=2048)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--rows", type=int, default=1_000_000)
