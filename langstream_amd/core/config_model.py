@@ -340,6 +340,10 @@ RESOURCE_MODELS: Dict[str, Model] = {
         "max-batch": I("Max concurrent sequences."), "max-seq-len": I("Max sequence length."),
         "kv-cache-dtype": S("Paged KV cache element type: auto (the model dtype), bf16 or fp8 (e4m3, twice the "
                             "tokens per kv-fraction); unset: the LS_KV_CACHE_DTYPE environment variable, else auto."),
+        "sliding-window": B("Serve a model-path with an active sliding window (Mistral, Qwen2 with "
+                            "use_sliding_window) over its whole position range, with windowed attention in the "
+                            "layers that have a window; false serves only the positions up to the window, with "
+                            "full attention; unset: the LS_SLIDING_WINDOW environment variable, else false."),
         "kv-k-scale": N("fp8 KV cache: K is stored as K / kv-k-scale.", default=1.0),
         "kv-v-scale": N("fp8 KV cache: V is stored as V / kv-v-scale.", default=1.0)},
         allow_unknown=True),

@@ -247,7 +247,8 @@ class LLMEngine:
                       "decode_tokens": 0, "preemptions": 0, "requests": 0, "finished": 0, "graph_steps": 0,
                       "host_ms": 0.0, "wait_ms": 0.0, "launch_ms": 0.0, "retire_ms": 0.0, "prefix_hit_tokens": 0,
                       "prompt_tokens": 0, "kv_cache_dtype": self.kv_cache_dtype,
-                      "kv_bytes_per_block": self.kv_bytes_per_block}
+                      "kv_bytes_per_block": self.kv_bytes_per_block,
+                      "sliding_window": int(getattr(model.cfg, "sliding_window", 0) or 0)}
         # prompt lengths of the most recent requests (decode attention cost follows the longest context)
         self.prompt_lens: collections.deque = collections.deque(maxlen=8192)
         # wall-clock (time.time) times at which requests reached the scheduler

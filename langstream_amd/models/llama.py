@@ -48,6 +48,19 @@ class LlamaConfig:
     bos_token_id: int = 128000
     eos_token_ids: tuple = (128001, 128009)
     qkv_bias: bool = False   # a bias on the fused QKV projection (Qwen2), added before RoPE
+    # sliding-window attention (Mistral, Qwen2): a windowed layer's query at position p sees the
+    # keys p - W < j <= p.  0: full attention.  window_layers: the windowed layer indices,
+    # None with a window: every layer
+    sliding_window: int = 0
+    window_layers: Optional[tuple] = None
+
+    def layer_window(self, i: int) -> int:
+        """The attention window of layer i (0: full attention)."""
+        if self.sliding_window <= 0:
+            return 0
+        if self.window_layers is None or i in self.window_layers:
+            return int(self.sliding_window)
+        return 0
 
     @property
     def num_params(self) -> int:
@@ -269,19 +282,21 @@ class LlamaModel:
                                k_scale=ks, v_scale=vs, bias=layer.qkv_b)
             q = qkv[:, : self.hq * D]
             nd = meta.num_decode
+            win = cfg.layer_window(li)
             if meta.num_prefill_tokens == 0:
                 attn = ops.paged_decode_attention(q, kc, vc, meta.d_block_tables, meta.d_ctx_lens, self.scale,
                                                   nsplit=meta.nsplit, blocks_per_split=meta.blocks_per_split,
-                                                  workspace=meta.workspace, k_scale=ks, v_scale=vs)
+                                                  workspace=meta.workspace, k_scale=ks, v_scale=vs, window=win)
             else:
                 attn = torch.empty(q.shape[0], self.hq * D, dtype=q.dtype, device=q.device)
                 if nd:
                     ops.paged_decode_attention(q[:nd], kc, vc, meta.d_block_tables, meta.d_ctx_lens, self.scale,
                                                out=attn[:nd], nsplit=meta.nsplit,
                                                blocks_per_split=meta.blocks_per_split, workspace=meta.workspace,
-                                               k_scale=ks, v_scale=vs)
+                                               k_scale=ks, v_scale=vs, window=win)
                 ops.paged_prefill_attention(q, kc, vc, meta.p_block_tables, meta.q_start, meta.q_len, meta.ctx_len,
-                                            meta.tiles, self.hq, self.scale, out=attn, k_scale=ks, v_scale=vs)
+                                            meta.tiles, self.hq, self.scale, out=attn, k_scale=ks, v_scale=vs,
+                                            window=win)
             o = _linear(attn, layer.o_w)
             self.tp.all_reduce(o)
             ops.fused_add_rmsnorm(o, residual, layer.post_norm, eps)
@@ -313,7 +328,8 @@ class LlamaModel:
             [l.down_w for l in L], [l.in_norm for l in L], [l.post_norm for l in L], self.final_norm,
             self.lm_head, [kv[0] for kv in kv_caches], [kv[1] for kv in kv_caches], self.cos_sin, self.hq,
             self.hkv, self.cfg.head_dim, self.cfg.rms_eps, self.scale, self.cfg.vocab_size, self.vocab_start, pg,
-            self.kv_k_scale, self.kv_v_scale, [l.qkv_b for l in L] if self.cfg.qkv_bias else None)
+            self.kv_k_scale, self.kv_v_scale, [l.qkv_b for l in L] if self.cfg.qkv_bias else None,
+            [self.cfg.layer_window(i) for i in range(len(L))])
         self._runner = (key, runner, kv_caches)
         return runner
 

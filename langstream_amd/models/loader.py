@@ -102,10 +102,38 @@ def _rope_from_hf(c: dict) -> Tuple[float, Optional[dict]]:
     return float(theta if theta is not None else 10000.0), scaling
 
 
-def llama_config_from_hf(model_dir: str) -> LlamaConfig:
+LAYER_TYPES = ("full_attention", "sliding_attention")
+
+
+def _window_layers_from_hf(c: dict, mtype: str) -> Optional[tuple]:
+    """The windowed layer indices of a checkpoint with an active sliding window, None for
+    every layer: ``layer_types`` where the config has it, else the family's rule (Mistral:
+    every layer; Qwen2: the layers ``i >= max_window_layers``)."""
+    n = int(c["num_hidden_layers"])
+    lt = c.get("layer_types")
+    if isinstance(lt, (list, tuple)) and lt:
+        if len(lt) != n:
+            raise ValueError(f"layer_types has {len(lt)} entries for {n} layers")
+        layers = tuple(i for i, t in enumerate(lt) if t == "sliding_attention")
+    elif mtype == "qwen2":
+        layers = tuple(range(min(int(c.get("max_window_layers", 28)), n), n))
+    else:
+        return None
+    return None if len(layers) == n else layers
+
+
+def llama_config_from_hf(model_dir: str, sliding_window: bool = False) -> LlamaConfig:
     """The shape of a Hugging Face ``llama`` / ``mistral`` / ``qwen2`` directory.  Anything
     the engine would compute differently from the checkpoint's own model is refused here
-    (other model types, other RoPE scalings) or in ``convert_hf_llama`` (other tensors)."""
+    (other model types, other RoPE scalings, other layer types) or in ``convert_hf_llama``
+    (other tensors).
+
+    A checkpoint with an active sliding window (Mistral's ``sliding_window``, Qwen2 with
+    ``use_sliding_window``) shorter than ``max_position_embeddings`` is served in one of two
+    ways.  ``sliding_window=False`` (the default): as a full-attention model up to the
+    window, ``max_position`` clamped to it.  ``True``: over its whole position range, with
+    the window in the attention kernels of the layers that have one
+    (``LlamaConfig.sliding_window`` / ``window_layers``)."""
     with open(os.path.join(model_dir, "config.json")) as f:
         c = json.load(f)
     mtype = c.get("model_type", "llama")
@@ -114,6 +142,9 @@ def llama_config_from_hf(model_dir: str) -> LlamaConfig:
     theta, scaling = _rope_from_hf(c)
     qkv_bias = mtype == "qwen2" or any(n.endswith("self_attn.q_proj.bias") for n in _checkpoint_names(model_dir))
     max_pos = c.get("max_position_embeddings", 8192)
+    for t in c.get("layer_types") or ():
+        if t not in LAYER_TYPES:
+            raise ValueError(f"unsupported layer type {t!r} in layer_types (supported: {', '.join(LAYER_TYPES)})")
     # an active sliding window: full attention equals windowed attention up to the window,
     # so positions past it are not served
     window = c.get("sliding_window")
@@ -121,7 +152,14 @@ def llama_config_from_hf(model_dir: str) -> LlamaConfig:
         window = None
     if mtype == "llama":
         window = None
-    if window:
+    win, win_layers = 0, None
+    if window and sliding_window and int(window) < max_pos:
+        win_layers = _window_layers_from_hf(c, mtype)
+        if win_layers is None or len(win_layers) > 0:
+            win = int(window)
+        else:
+            win_layers = None   # no layer is windowed: a full-attention model
+    elif window:
         max_pos = min(max_pos, int(window))
     eos = c.get("eos_token_id", 2)
     eos = list(eos) if isinstance(eos, (list, tuple)) else [eos]
@@ -143,7 +181,7 @@ def llama_config_from_hf(model_dir: str) -> LlamaConfig:
         rope_theta=theta, rope_scaling=scaling,
         rms_eps=c.get("rms_norm_eps", 1e-5), max_position=max_pos,
         tie_embeddings=bool(c.get("tie_word_embeddings", False)), bos_token_id=1 if bos is None else bos,
-        eos_token_ids=tuple(eos), qkv_bias=qkv_bias)
+        eos_token_ids=tuple(eos), qkv_bias=qkv_bias, sliding_window=win, window_layers=win_layers)
 
 
 def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = None) -> Dict[str, torch.Tensor]:

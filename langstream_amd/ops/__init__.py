@@ -259,11 +259,21 @@ def decode_splits(max_blocks: int, min_blocks_per_split: int = 0) -> tuple[int, 
     return nsplit, bps
 
 
+def _window(window) -> int:
+    """A sliding-window size: 0 is no window; negative sizes are refused."""
+    window = int(window)
+    if window < 0:
+        raise ValueError(f"attention window must be >= 0 (0: no window), got {window}")
+    return window
+
+
 def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale, out=None,
                            nsplit: int = 1, blocks_per_split: int = 1 << 30, workspace=None,
-                           k_scale: float = 1.0, v_scale: float = 1.0):
+                           k_scale: float = 1.0, v_scale: float = 1.0, window: int = 0):
     """q: [B, Hq*D] (may be a strided view into the QKV buffer); returns [B, Hq*D].
-    k_scale / v_scale: the scales of an fp8 cache (ignored by bf16 caches)."""
+    k_scale / v_scale: the scales of an fp8 cache (ignored by bf16 caches).
+    window > 0: sliding-window attention, row b sees its last `window` keys only."""
+    window = _window(window)
     B = ctx_lens.shape[0]
     D = k_cache.shape[3]
     Hq = q.shape[-1] // D if q.dim() == 2 else q.shape[1]
@@ -273,10 +283,10 @@ def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale, o
             assert workspace is not None and workspace.numel() >= B * Hq * nsplit * (D + 2)
         ws = workspace if workspace is not None else out.new_empty(0, dtype=torch.float32)
         hip().paged_decode_attention(out, q, k_cache, v_cache, block_tables, ctx_lens, scale, nsplit,
-                                     min(blocks_per_split, block_tables.shape[1]), ws, k_scale, v_scale)
+                                     min(blocks_per_split, block_tables.shape[1]), ws, k_scale, v_scale, window)
         return out
     r = ref.paged_decode_attention(q.reshape(B, Hq, D), k_cache, v_cache, block_tables, ctx_lens, scale,
-                                   k_scale, v_scale)
+                                   k_scale, v_scale, window)
     r = r.reshape(B, Hq * D)
     if out is not None:
         out.copy_(r)
@@ -286,11 +296,13 @@ def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale, o
 
 def paged_decode_attention_rope(qkv, pos, cos_sin, slots, k_cache, v_cache, block_tables, ctx_lens, scale,
                                 Hq: int, out=None, nsplit: int = 1, blocks_per_split: int = 1 << 30,
-                                workspace=None):
+                                workspace=None, window: int = 0):
     """Decode-only step with RoPE + the KV-cache write fused into attention.  qkv:
     [B, (Hq + 2 Hkv) D] un-rotated projection rows (left unmodified); the new token of
     each row (ctx_lens count it) is written to the cache at ``slots`` and attended from
-    registers.  Returns [B, Hq*D]; numerically rope_and_cache + paged_decode_attention."""
+    registers.  Returns [B, Hq*D]; numerically rope_and_cache + paged_decode_attention.
+    window > 0: sliding-window attention (the new token counts as one of the window keys)."""
+    window = _window(window)
     B = ctx_lens.shape[0]
     D = k_cache.shape[3]
     Hkv = k_cache.shape[1]
@@ -300,11 +312,13 @@ def paged_decode_attention_rope(qkv, pos, cos_sin, slots, k_cache, v_cache, bloc
             assert workspace is not None and workspace.numel() >= B * Hq * nsplit * (D + 2)
         ws = workspace if workspace is not None else out.new_empty(0, dtype=torch.float32)
         hip().paged_decode_attention_rope(out, qkv, pos, cos_sin, slots, k_cache, v_cache, block_tables, ctx_lens,
-                                          scale, nsplit, min(blocks_per_split, block_tables.shape[1]), ws)
+                                          scale, nsplit, min(blocks_per_split, block_tables.shape[1]), ws,
+                                          window)
         return out
     work = qkv.clone()
     ref.rope_and_cache(work, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, True)
-    return paged_decode_attention(work[:, : Hq * D], k_cache, v_cache, block_tables, ctx_lens, scale, out=out)
+    return paged_decode_attention(work[:, : Hq * D], k_cache, v_cache, block_tables, ctx_lens, scale, out=out,
+                                  window=window)
 
 
 def prefill_tiles(q_lens: Sequence[int], G: int, prefix_lens: Sequence[int] | None = None) -> torch.Tensor:
@@ -345,16 +359,18 @@ def prefill_tiles_np(q_lens, G: int, prefix_lens, out=None):
 
 
 def paged_prefill_attention(q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, tiles, Hq, scale,
-                            out=None, k_scale: float = 1.0, v_scale: float = 1.0):
+                            out=None, k_scale: float = 1.0, v_scale: float = 1.0, window: int = 0):
+    """window > 0: sliding-window attention, the token at position p sees keys p - window < j <= p."""
+    window = _window(window)
     T = q.shape[0]
     D = k_cache.shape[3]
     if _gpu(q):
         out = torch.empty(T, Hq * D, dtype=q.dtype, device=q.device) if out is None else out
         hip().paged_prefill_attention(out, q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, tiles,
-                                      Hq, scale, k_scale, v_scale)
+                                      Hq, scale, k_scale, v_scale, window)
         return out
     r = ref.paged_prefill_attention(q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, Hq, scale,
-                                    k_scale, v_scale)
+                                    k_scale, v_scale, window)
     if out is None:
         return r
     for s, n in zip(q_start.tolist(), q_len.tolist()):

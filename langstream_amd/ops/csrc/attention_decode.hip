@@ -28,6 +28,13 @@
 // context evenly over the S splits (bps = max(min_bps, ceil(nblk / S)), computed on
 // the device), so the grid carries no idle workgroups for short sequences.
 //
+// Sliding window (window > 0, a runtime argument of the same instantiations): a sequence
+// visits only the blocks from its first visible key on, the splits divide those blocks
+// (decode_plan below), and keys before the window in the first visited block are masked
+// with the tail.  Measured (tools/attn_bench.py --ring 3 --window 4096,
+// profiles/r10/sliding_window/): B = 16 ctx 16384 53.9 us against 181.8 us unwindowed (ctx
+// 4096: 54.3 us); B = 64 ctx 8192 181.1 against 336.4 us (ctx 4096: 169.5 us).
+//
 // Memory path: K and V fragments are raw buffer loads through per-block descriptors
 // (wave-uniform, readfirstlane'd).  The K descriptor covers only the block's valid
 // keys and masked V groups get an out-of-range offset, so the tail of a sequence's
@@ -64,6 +71,31 @@ __device__ __forceinline__ int split_blocks(int nblk, int nsplit, int min_bps) {
   return max(min_bps, (nblk + nsplit - 1) / nsplit);
 }
 
+// Sliding window (window > 0): the query at position ctx_all - 1 sees the `window` keys
+// lo = max(0, ctx_all - window) .. ctx_all - 1; window = 0 is lo = 0, every key.  The KV
+// blocks b0 = lo / 64 .. nblk - 1 are the only ones visited, and the splits divide THAT
+// range, bps blocks each.  The attention kernel and the merge kernel both take the plan
+// from here, so they cannot disagree on which splits exist.  ctx_adj = 1 in the fused-RoPE
+// form, where the last key comes from registers and the cache holds ctx_all - 1 keys: at
+// window = 1 (lo == ctx) no cached key is visible and no block is visited.
+struct DecodePlan {
+  int ctx;   // keys read from the cache
+  int lo;    // first visible key
+  int b0;    // first visited block
+  int nblk;  // one past the last visited block
+  int bps;   // blocks per split
+};
+__device__ __forceinline__ DecodePlan decode_plan(int ctx_all, int ctx_adj, int window, int max_blocks, int nsplit,
+                                                  int min_bps) {
+  DecodePlan p;
+  p.ctx = max(ctx_all - ctx_adj, 0);
+  p.nblk = min((p.ctx + BS - 1) / BS, max_blocks);
+  p.lo = window > 0 ? max(ctx_all - window, 0) : 0;
+  p.b0 = p.lo < p.ctx ? min(p.lo / BS, p.nblk) : p.nblk;
+  p.bps = split_blocks(p.nblk - p.b0, nsplit, min_bps);
+  return p;
+}
+
 // Fused RoPE + KV write (ROPE = true, decode-only steps): q holds the UN-rotated QKV
 // projection rows [B, (Hq + 2 Hkv) D].  Every wave rotates its Q^T fragments in
 // registers (a lane's dims 32ks + 8h + j, ks < KS/2, pair with the +D/2 dims of ks + KS/2
@@ -90,7 +122,7 @@ __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2
     bf16* __restrict__ out, const bf16* __restrict__ q, int64_t q_stride, const bf16* __restrict__ kc,
     const bf16* __restrict__ vc, const int32_t* __restrict__ block_tables, int max_blocks,
     const int32_t* __restrict__ ctx_lens, int Hkv, int G, int NB, float scale_log2, int min_bps,
-    float* __restrict__ part_o, float* __restrict__ part_ml, KvWrite kw, float v_scale) {
+    float* __restrict__ part_o, float* __restrict__ part_ml, KvWrite kw, float v_scale, int window) {
   static_assert(!(F8 && ROPE), "the fused-RoPE form writes bf16 K/V");
   constexpr int EB = F8 ? 1 : 2;  // bytes per cache element
   using Frag = std::conditional_t<F8, uint2, uint4>;  // 8 cache elements
@@ -116,17 +148,16 @@ __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2
   const int ctx_all = ctx_lens[b];
   const float* cs = ROPE ? kv_cos_sin_row(kw, b, D) : nullptr;  // the new token's cos / sin
   // keys read from the cache: with ROPE the new token (the last one) comes from registers
-  const int ctx = ROPE ? max(ctx_all - 1, 0) : ctx_all;
-  const int nblk = min((ctx + BS - 1) / BS, max_blocks);
-  const int bps = split_blocks(nblk, nsplit, min_bps);
-  const int bstart = split * bps;
+  const DecodePlan plan = decode_plan(ctx_all, ROPE ? 1 : 0, window, max_blocks, nsplit, min_bps);
+  const int ctx = plan.ctx, nblk = plan.nblk, bps = plan.bps;
+  const int bstart = plan.b0 + split * bps;
   const int bend = min(nblk, bstart + bps);
   // splits past this sequence's context exit at once; the merge kernel only reads
   // the ceil(nblk / bps) splits that exist.
   if (split > 0 && bstart >= nblk) return;
   // a context that fits in one split (short chats at small batch) is finished here:
   // split 0 writes the normalised bf16 row and the merge kernel skips it
-  const bool single = nsplit == 1 || nblk <= bps;
+  const bool single = nsplit == 1 || nblk - plan.b0 <= bps;
 
   // Q^T fragments (B operand): lane holds Q[head kvh*G + i16][32ks + 8h .. +7]
   bf16x8 qf[KS];
@@ -305,7 +336,10 @@ __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2
       s[kt] = acc;
     }
     // ---- online softmax (row = qrow = lane&15; this lane holds 16 of the 64 keys)
-    const int kbase = bi * BS;
+    // visible: lo <= key < ctx, as one unsigned compare of key - lo (a visited block has
+    // lo < ctx; keys below lo wrap to large values)
+    const int kbase = bi * BS - plan.lo;
+    const unsigned span = (unsigned)(ctx - plan.lo);
     float mx = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
@@ -313,7 +347,7 @@ __global__ void __launch_bounds__(64 * WPP) __attribute__((amdgpu_waves_per_eu(2
       for (int r = 0; r < 4; ++r) {
         const int key = kbase + 32 * (kt >> 1) + 8 * h + 4 * (kt & 1) + r;
         float v = s[kt][r] * scale_log2;
-        v = key < ctx ? v : -INFINITY;
+        v = (unsigned)key < span ? v : -INFINITY;
         s[kt][r] = v;
         mx = fmaxf(mx, v);
       }
@@ -456,16 +490,16 @@ template <int D>
 __global__ void __launch_bounds__(256) decode_merge_kernel(bf16* __restrict__ out, const float* __restrict__ part_o,
                                                            const float* __restrict__ part_ml, int nsplit_grid, int nrows,
                                                            const int32_t* __restrict__ ctx_lens, int Hq, int min_bps,
-                                                           int max_blocks, int ctx_adj) {
+                                                           int max_blocks, int ctx_adj, int window) {
   // one wave per (b, head) row; lanes over d
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= nrows) return;
   // ctx_adj = 1 under ROPE: the split kernel covered the ctx - 1 cached keys
-  const int nblk = min((max(ctx_lens[row / Hq] - ctx_adj, 0) + BS - 1) / BS, max_blocks);
-  const int bps = split_blocks(nblk, nsplit_grid, min_bps);
-  const int nsplit = max(1, min(nsplit_grid, (nblk + bps - 1) / bps));
-  if (nblk <= bps) return;   // one split: the attention kernel wrote the row itself
+  const DecodePlan plan = decode_plan(ctx_lens[row / Hq], ctx_adj, window, max_blocks, nsplit_grid, min_bps);
+  const int nvis = plan.nblk - plan.b0, bps = plan.bps;
+  const int nsplit = max(1, min(nsplit_grid, (nvis + bps - 1) / bps));
+  if (nvis <= bps) return;   // one split: the attention kernel wrote the row itself
   const float* ml = part_ml + (int64_t)row * nsplit_grid * 2;
   float mstar = -1e30f;
   for (int s = 0; s < nsplit; ++s) mstar = fmaxf(mstar, ml[2 * s]);
@@ -495,8 +529,8 @@ int64_t decode_nsplit(int64_t B, int64_t Hkv, int64_t nsplit_max) {
 static void decode_attention_launch(at::Tensor& out, const at::Tensor& q, const at::Tensor& k_cache,
                                     const at::Tensor& v_cache, const at::Tensor& block_tables,
                                     const at::Tensor& ctx_lens, double scale, int64_t nsplit, int64_t min_bps,
-                                    const at::Tensor& workspace, const KvWrite* kw, double k_scale = 1.0,
-                                    double v_scale = 1.0) {
+                                    const at::Tensor& workspace, const KvWrite* kw, int64_t window,
+                                    double k_scale = 1.0, double v_scale = 1.0) {
   const bool f8 = kv_is_fp8(k_cache, v_cache, "paged_decode_attention");
   TORCH_CHECK(!f8 || (k_scale > 0.0 && v_scale > 0.0), "KV cache scales must be positive");
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16);
@@ -514,6 +548,7 @@ static void decode_attention_launch(at::Tensor& out, const at::Tensor& q, const 
   TORCH_CHECK(block_tables.scalar_type() == at::kInt && block_tables.is_contiguous() && block_tables.size(0) == B);
   TORCH_CHECK(ctx_lens.scalar_type() == at::kInt && ctx_lens.is_contiguous());
   TORCH_CHECK(nsplit >= 1 && min_bps >= 1);
+  TORCH_CHECK(window >= 0 && window <= INT32_MAX, "attention window must be >= 0 (0: no window), got ", window);
   const int64_t q_stride = q.dim() >= 2 ? q.stride(0) : (int64_t)Hq * D;
   TORCH_CHECK(q_stride % 8 == 0);
   if (B == 0) return;
@@ -557,7 +592,8 @@ static void decode_attention_launch(at::Tensor& out, const at::Tensor& q, const 
   decode_attn_kernel<DD, W, P, R, A, F><<<grid, 64 * W, 0, stream>>>(                                         \
       (bf16*)out.data_ptr(), (const bf16*)q.data_ptr(), q_stride, (const bf16*)k_cache.data_ptr(),            \
       (const bf16*)v_cache.data_ptr(), block_tables.data_ptr<int32_t>(), (int)block_tables.size(1),          \
-      ctx_lens.data_ptr<int32_t>(), Hkv, G, (int)k_cache.size(0), sl2, (int)min_bps, po, pml, rargs, vs)
+      ctx_lens.data_ptr<int32_t>(), Hkv, G, (int)k_cache.size(0), sl2, (int)min_bps, po, pml, rargs, vs,  \
+      (int)window)
 #define LAUNCH_P(DD, W, P) \
   if (rope) LAUNCH_R(DD, W, P, true); else LAUNCH_R(DD, W, P, false)
 #define LAUNCH_K(DD, W) \
@@ -567,7 +603,8 @@ static void decode_attention_launch(at::Tensor& out, const at::Tensor& q, const 
   if (ns > 1)                                                                                                 \
     decode_merge_kernel<DD><<<(B * Hq + 3) / 4, 256, 0, stream>>>((bf16*)out.data_ptr(), po, pml, (int)ns,    \
                                                                   B * Hq, ctx_lens.data_ptr<int32_t>(), Hq,    \
-                                                                  (int)min_bps, (int)block_tables.size(1), rope ? 1 : 0)
+                                                                  (int)min_bps, (int)block_tables.size(1), rope ? 1 : 0, \
+                                                                  (int)window)
   if (D == 128) { LAUNCH(128); }
   else if (D == 64) { LAUNCH(64); }
   else TORCH_CHECK(false, "unsupported head dim ", D);
@@ -582,9 +619,10 @@ static void decode_attention_launch(at::Tensor& out, const at::Tensor& q, const 
 
 void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
                             at::Tensor block_tables, at::Tensor ctx_lens, double scale, int64_t nsplit,
-                            int64_t min_bps, at::Tensor workspace, double k_scale, double v_scale) {
+                            int64_t min_bps, at::Tensor workspace, double k_scale, double v_scale,
+                            int64_t window) {
   decode_attention_launch(out, q, k_cache, v_cache, block_tables, ctx_lens, scale, nsplit, min_bps, workspace,
-                          nullptr, k_scale, v_scale);
+                          nullptr, window, k_scale, v_scale);
 }
 
 // Decode-only step with RoPE and the KV-cache write fused in (see above).
@@ -593,7 +631,7 @@ void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at
 void paged_decode_attention_rope(at::Tensor out, at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin,
                                  at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, at::Tensor block_tables,
                                  at::Tensor ctx_lens, double scale, int64_t nsplit, int64_t min_bps,
-                                 at::Tensor workspace) {
+                                 at::Tensor workspace, int64_t window) {
   TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 2 && qkv.stride(1) == 1, "qkv must be [B, (Hq + 2 Hkv) D]");
   TORCH_CHECK(k_cache.dim() == 4, "k_cache [NB, Hkv, 64, D]");
   const int64_t Hkv = k_cache.size(1), D = k_cache.size(3), B = ctx_lens.numel();
@@ -604,5 +642,5 @@ void paged_decode_attention_rope(at::Tensor out, at::Tensor qkv, at::Tensor pos,
   TORCH_CHECK(qkv.size(1) == (Hq + 2 * Hkv) * D, "qkv width must be (Hq + 2 Hkv) * D");
   TORCH_CHECK(pos.is_contiguous() && slots.is_contiguous());
   decode_attention_launch(out, qkv, k_cache, v_cache, block_tables, ctx_lens, scale, nsplit, min_bps, workspace,
-                          &kw);
+                          &kw, window);
 }

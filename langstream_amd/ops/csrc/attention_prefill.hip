@@ -5,7 +5,9 @@
 //
 //  * PAGED=true  (Llama prefill, incl. chunked prefill with a cached prefix):
 //      K from k_cache [NB, Hkv, 64, D], V^T from v_cache [NB, Hkv, 8, D, 8] (8-key groups,
-//      common.h vt_off), causal.
+//      common.h vt_off), causal; window > 0 (the WIN instantiations) also hides the keys at
+//      or below p - window from the row at position p, and KV tiles before the first row's
+//      window are not visited.
 //  * PAGED=false (BERT encoder): K and V read from the packed QKV projection,
 //      bidirectional, keys limited to the sequence (padding-free varlen).
 //
@@ -48,13 +50,18 @@ struct SeqMeta {
 // 8 bytes each, and store_tile decodes them into the same bf16 LDS image; everything after
 // store_tile is the bf16 kernel.  The host folds k_scale into scale_log2; v_scale
 // multiplies the f32 output once in the epilogue.
-template <int D, bool PAGED, bool F8 = false>
+// WIN (PAGED only): sliding-window attention, the `window` argument > 0.  A template flag,
+// so a launch without a window runs the instantiation it always ran: with the window as a
+// runtime bound of one kernel the compiler re-allocated the bf16 D = 128 form (246 -> 216
+// VGPRs) and it measured 2 to 5 % slower at window = 0 (profiles/r10/sliding_window/).
+template <int D, bool PAGED, bool F8 = false, bool WIN = false>
 __global__ void __launch_bounds__(256, 2) prefill_attn_kernel(
     bf16* __restrict__ out, const bf16* __restrict__ q, int64_t q_stride, const bf16* __restrict__ kc,
     const bf16* __restrict__ vc, const int32_t* __restrict__ block_tables, int max_blocks, int NB,
     SeqMeta meta, const int32_t* __restrict__ tiles, int Hq, int Hkv, float scale_log2, int64_t out_stride,
-    float v_scale) {
+    float v_scale, int window) {
   static_assert(PAGED || !F8, "fp8 is a KV-cache format");
+  static_assert(PAGED || !WIN, "the encoder takes no window");
   using Chunk = std::conditional_t<F8, uint2, uint4>;  // 8 cache elements
   constexpr int KS = D / 32;
   constexpr int DT = D / 16;
@@ -95,6 +102,12 @@ __global__ void __launch_bounds__(256, 2) prefill_attn_kernel(
   const int last_row = min(r0 + ROWS, nrows) - 1;
   const int kmax = PAGED ? min(cl, prefix + last_row / G + 1) : cl;
   const int ntiles = (kmax + KVT - 1) / KVT;
+  // Sliding window (WIN): the row at position p sees the keys p - window < key <= p.  The
+  // workgroup's FIRST row has the lowest position, so the tile that holds its first visible
+  // key is the first one any row needs.  Both sides of the mask are one unsigned compare of
+  // p - key against the window (a key past p, and every key of a padding row p = -1, wraps
+  // to a large value).
+  const int t0 = WIN ? max(prefix + r0 / G - window + 1, 0) / KVT : 0;
 
   f32x4 o[2][DT];
 #pragma unroll
@@ -174,8 +187,11 @@ __global__ void __launch_bounds__(256, 2) prefill_attn_kernel(
     }
   };
 
-  if (ntiles > 0) load_tile(0);
-  for (int t = 0; t < ntiles; ++t) {
+  // A later row subtile can meet whole tiles before its own first visible key: every score
+  // is -inf there, mnew stays at the -1e30 floor, alpha = 1 and p = 0, so l and O are untouched
+  // (what a padding row goes through on every tile).
+  if (t0 < ntiles) load_tile(t0);   // without WIN: t0 = 0, the loop of old
+  for (int t = t0; t < ntiles; ++t) {
     __syncthreads();  // everyone finished reading the previous tile
     store_tile();
     __syncthreads();
@@ -206,7 +222,8 @@ __global__ void __launch_bounds__(256, 2) prefill_attn_kernel(
         for (int r = 0; r < 4; ++r) {
           const int key = kbase + 32 * (kt >> 1) + 8 * h + 4 * (kt & 1) + r;
           float v = s[n][kt][r] * scale_log2;
-          const bool ok = PAGED ? (key <= rowpos[n]) : (key < cl && rowpos[n] >= 0);
+          const bool ok = WIN ? (unsigned)(rowpos[n] - key) < (unsigned)window
+                              : PAGED ? (key <= rowpos[n]) : (key < cl && rowpos[n] >= 0);
           v = ok ? v : -INFINITY;
           s[n][kt][r] = v;
           mx = fmaxf(mx, v);
@@ -277,7 +294,8 @@ __global__ void __launch_bounds__(256, 2) prefill_attn_kernel(
 // tiles: [ntiles, 2] int32 (seq, first row) with rows = token*G + g, 128 rows per tile.
 void paged_prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
                              at::Tensor block_tables, at::Tensor q_start, at::Tensor q_len, at::Tensor ctx_len,
-                             at::Tensor tiles, int64_t Hq, double scale, double k_scale, double v_scale) {
+                             at::Tensor tiles, int64_t Hq, double scale, double k_scale, double v_scale,
+                             int64_t window) {
   const bool f8 = kv_is_fp8(k_cache, v_cache, "paged_prefill_attention");
   TORCH_CHECK(!f8 || (k_scale > 0.0 && v_scale > 0.0), "KV cache scales must be positive");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16 && q.stride(-1) == 1);
@@ -285,6 +303,7 @@ void paged_prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, a
               v_cache.size(4) == 8, "KV block size must be 64 (v_cache [NB, Hkv, 8, D, 8])");
   const int Hkv = k_cache.size(1), D = k_cache.size(3);
   TORCH_CHECK(Hq % Hkv == 0 && v_cache.size(3) == D);
+  TORCH_CHECK(window >= 0 && window <= INT32_MAX, "attention window must be >= 0 (0: no window), got ", window);
   for (auto* t : {&block_tables, &q_start, &q_len, &ctx_len, &tiles})
     TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous());
   TORCH_CHECK(out.stride(-1) == 1 && q.stride(0) % 8 == 0 && out.stride(0) % 4 == 0);
@@ -296,11 +315,13 @@ void paged_prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, a
   // fp8: the K scale folds into the softmax scale
   const float sl2 = f8 ? (float)scale * (float)k_scale * LOG2E_P : (float)scale * LOG2E_P;
   const float vs = f8 ? (float)v_scale : 1.f;
-#define LAUNCH_F(DD, FF)                                                                                             \
-  prefill_attn_kernel<DD, true, FF><<<grid, 256, 0, stream>>>(                                                      \
+#define LAUNCH_F(DD, FF) \
+  if (window > 0) LAUNCH_W(DD, FF, true); else LAUNCH_W(DD, FF, false)
+#define LAUNCH_W(DD, FF, WW)                                                                                         \
+  prefill_attn_kernel<DD, true, FF, WW><<<grid, 256, 0, stream>>>(                                                      \
       (bf16*)out.data_ptr(), (const bf16*)q.data_ptr(), q.stride(0), (const bf16*)k_cache.data_ptr(),              \
       (const bf16*)v_cache.data_ptr(), block_tables.data_ptr<int32_t>(), (int)block_tables.size(1),                 \
-      (int)k_cache.size(0), meta, tiles.data_ptr<int32_t>(), (int)Hq, Hkv, sl2, out.stride(0), vs)
+      (int)k_cache.size(0), meta, tiles.data_ptr<int32_t>(), (int)Hq, Hkv, sl2, out.stride(0), vs, (int)window)
 #define LAUNCH(DD) \
   if (f8) LAUNCH_F(DD, true); else LAUNCH_F(DD, false)
   if (D == 128) { LAUNCH(128); }
@@ -308,6 +329,7 @@ void paged_prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, a
   else TORCH_CHECK(false, "unsupported head dim ", D);
 #undef LAUNCH
 #undef LAUNCH_F
+#undef LAUNCH_W
 }
 
 // Dense bidirectional varlen attention over a packed QKV tensor [T, (Hq+2Hkv)*D]
@@ -329,7 +351,7 @@ void varlen_encoder_attention(at::Tensor out, at::Tensor qkv, at::Tensor q_start
   prefill_attn_kernel<DD, false><<<grid, 256, 0, stream>>>((bf16*)out.data_ptr(), base, qkv.stride(0),  \
                                                            base, base, nullptr, 1, 1, meta,             \
                                                            tiles.data_ptr<int32_t>(), (int)Hq, (int)Hkv, \
-                                                           sl2, out.stride(0), 1.f)
+                                                           sl2, out.stride(0), 1.f, 0)
   if (D == 32) LAUNCH(32);
   else if (D == 64) LAUNCH(64);
   else if (D == 128) LAUNCH(128);

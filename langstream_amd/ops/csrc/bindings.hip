@@ -9,17 +9,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embed_layernorm", &embed_layernorm);
   m.def("silu_and_mul", &silu_and_mul);
   m.def("bias_gelu", &bias_gelu);
+  // window (the attention ops): > 0 limits a query at position p to the keys p - window < key <= p; 0: no window
   // k_scale / v_scale: the per-engine scales of an fp8 (float8_e4m3fn) KV cache; bf16 caches ignore them
   m.def("rope_and_cache", &rope_and_cache, py::arg("qkv"), py::arg("pos"), py::arg("cos_sin"), py::arg("slots"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("Hq"), py::arg("Hkv"), py::arg("apply_rope"),
         py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0, py::arg("bias") = py::none());
   m.def("paged_decode_attention", &paged_decode_attention, py::arg("out"), py::arg("q"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("block_tables"), py::arg("ctx_lens"), py::arg("scale"), py::arg("nsplit"),
-        py::arg("blocks_per_split"), py::arg("workspace"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0);
-  m.def("paged_decode_attention_rope", &paged_decode_attention_rope);
+        py::arg("blocks_per_split"), py::arg("workspace"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0,
+        py::arg("window") = 0);
+  m.def("paged_decode_attention_rope", &paged_decode_attention_rope, py::arg("out"), py::arg("qkv"), py::arg("pos"),
+        py::arg("cos_sin"), py::arg("slots"), py::arg("k_cache"), py::arg("v_cache"), py::arg("block_tables"),
+        py::arg("ctx_lens"), py::arg("scale"), py::arg("nsplit"), py::arg("blocks_per_split"), py::arg("workspace"),
+        py::arg("window") = 0);
   m.def("paged_prefill_attention", &paged_prefill_attention, py::arg("out"), py::arg("q"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("block_tables"), py::arg("q_start"), py::arg("q_len"), py::arg("ctx_len"),
-        py::arg("tiles"), py::arg("Hq"), py::arg("scale"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0);
+        py::arg("tiles"), py::arg("Hq"), py::arg("scale"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0,
+        py::arg("window") = 0);
   m.def("varlen_encoder_attention", &varlen_encoder_attention);
   m.def("sample_tokens", &sample_tokens);
   m.def("apply_logit_deltas", &apply_logit_deltas);

@@ -85,16 +85,18 @@ void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tens
 // ---------------------------------------------------------------- attention_decode.hip
 void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
                             at::Tensor block_tables, at::Tensor ctx_lens, double scale, int64_t nsplit,
-                            int64_t blocks_per_split, at::Tensor workspace, double k_scale, double v_scale);
+                            int64_t blocks_per_split, at::Tensor workspace, double k_scale, double v_scale,
+                            int64_t window);
 void paged_decode_attention_rope(at::Tensor out, at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin,
                                  at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, at::Tensor block_tables,
                                  at::Tensor ctx_lens, double scale, int64_t nsplit, int64_t min_bps,
-                                 at::Tensor workspace);
+                                 at::Tensor workspace, int64_t window);
 
 // --------------------------------------------------------------- attention_prefill.hip
 void paged_prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
                              at::Tensor block_tables, at::Tensor q_start, at::Tensor q_len, at::Tensor ctx_len,
-                             at::Tensor tiles, int64_t Hq, double scale, double k_scale, double v_scale);
+                             at::Tensor tiles, int64_t Hq, double scale, double k_scale, double v_scale,
+                             int64_t window);
 void varlen_encoder_attention(at::Tensor out, at::Tensor qkv, at::Tensor q_start, at::Tensor q_len,
                               at::Tensor tiles, int64_t Hq, int64_t Hkv, double scale);
 

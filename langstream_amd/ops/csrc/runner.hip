@@ -96,7 +96,8 @@ class LlamaRunner {
               std::vector<at::Tensor> k_caches, std::vector<at::Tensor> v_caches, at::Tensor cos_sin, int64_t hq,
               int64_t hkv, int64_t head_dim, double eps, double scale, int64_t vocab_size, int64_t vocab_start,
               py::object process_group, double k_scale = 1.0, double v_scale = 1.0,
-              c10::optional<std::vector<at::Tensor>> qkv_b = c10::nullopt)
+              c10::optional<std::vector<at::Tensor>> qkv_b = c10::nullopt,
+              c10::optional<std::vector<int64_t>> windows = c10::nullopt)
       : embed_(embed), qkv_w_(qkv_w), o_w_(o_w), gate_up_w_(gate_up_w), down_w_(down_w), in_norm_(in_norm),
         post_norm_(post_norm), final_norm_(final_norm), lm_head_(lm_head), kc_(k_caches), vc_(v_caches),
         cos_sin_(cos_sin), hq_(hq), hkv_(hkv), d_(head_dim), eps_(eps), scale_(scale), vocab_(vocab_size),
@@ -117,6 +118,16 @@ class LlamaRunner {
       TORCH_CHECK(qkv_b_.size() == L, "LlamaRunner: one qkv bias per layer");
       for (size_t l = 0; l < L; ++l) qkv_bias_ptr("LlamaRunner", qkv_b_[l], qkv_w_[l], qkv_w_[l].size(0));
       bias_ = true;
+    }
+    // sliding-window attention: one window per layer (0: full attention), a model constant
+    // handed to every attention launch of that layer; without the list every layer is full
+    window_.assign(L, 0);
+    if (windows.has_value() && !windows->empty()) {
+      TORCH_CHECK(windows->size() == L, "LlamaRunner: one attention window per layer");
+      for (size_t l = 0; l < L; ++l) {
+        TORCH_CHECK((*windows)[l] >= 0, "LlamaRunner: attention windows must be >= 0 (0: no window)");
+        window_[l] = (*windows)[l];
+      }
     }
     if (!process_group.is_none()) pg_ = py::cast<c10::intrusive_ptr<::c10d::ProcessGroup>>(process_group);
     // LS_ONESHOT_AR=1: decode-sized all-reduces (<= LS_ONESHOT_AR_MAX elements, default
@@ -324,7 +335,7 @@ class LlamaRunner {
       if (!roped && decode_only && !f8_ && !bias_ && rope_fused()) {
         // decode-only step: RoPE + K/V cache write inside the attention kernel
         paged_decode_attention_rope(attn, qkv, pos, cos_sin_, slots, kc_[l], vc_[l], d_bt, d_ctx, scale_, nsplit,
-                                    bps, ws);
+                                    bps, ws, window_[l]);
         return attn;
       }
       if (!roped)
@@ -332,10 +343,10 @@ class LlamaRunner {
       at::Tensor q = qkv.narrow(1, 0, hq_ * d_);
       if (num_decode > 0)
         paged_decode_attention(attn.narrow(0, 0, num_decode), q.narrow(0, 0, num_decode), kc_[l], vc_[l], d_bt,
-                               d_ctx, scale_, nsplit, bps, ws, k_scale_, v_scale_);
+                               d_ctx, scale_, nsplit, bps, ws, k_scale_, v_scale_, window_[l]);
       if (num_prefill > 0)
         paged_prefill_attention(attn, q, kc_[l], vc_[l], p_bt, q_start, q_len, ctx_len, tiles, hq_, scale_, k_scale_,
-                                v_scale_);
+                                v_scale_, window_[l]);
       return attn;
     };
     // TP = 1: the residual add + RMSNorm after o_proj and down_proj run in the PROLOGUE of
@@ -462,7 +473,7 @@ class LlamaRunner {
                           kc_[l], vc_[l], hq_, hkv_, err);
       at::Tensor attn = at::empty({T, hq_ * d_}, h.options());
       paged_decode_attention(attn, qkv.narrow(1, 0, hq_ * d_), kc_[l], vc_[l], d_bt, d_ctx, scale_, nsplit, bps, ws,
-                             1.0, 1.0);
+                             1.0, 1.0, window_[l]);
       decode_gemm_res(y2, attn, o_w_[l], dg_ws_, cnt_o_, h, post_norm_[l], ss_post, err);
       at::Tensor a = at::empty({T, gate_up_w_[l].size(0) / 2}, h.options());
       decode_gemm_silu_r(a, y2, gate_up_w_[l], ss_post, eps_);
@@ -717,6 +728,7 @@ class LlamaRunner {
   bool f8_ = false;            // the KV caches are float8_e4m3fn
   std::vector<at::Tensor> qkv_b_;   // per-layer bias of the QKV projection, empty without
   bool bias_ = false;
+  std::vector<int64_t> window_;     // per-layer attention window, 0: full attention
   c10::optional<at::Tensor> bias(int64_t l) const {
     return bias_ ? c10::optional<at::Tensor>(qkv_b_[l]) : c10::nullopt;
   }
@@ -1342,13 +1354,13 @@ void bind_runners(py::module_& m) {
                     std::vector<at::Tensor>, std::vector<at::Tensor>, std::vector<at::Tensor>, at::Tensor, at::Tensor,
                     std::vector<at::Tensor>, std::vector<at::Tensor>, at::Tensor, int64_t, int64_t, int64_t, double,
                     double, int64_t, int64_t, py::object, double, double,
-                    c10::optional<std::vector<at::Tensor>>>(),
+                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<int64_t>>>(),
            py::arg("embed"), py::arg("qkv_w"), py::arg("o_w"), py::arg("gate_up_w"), py::arg("down_w"),
            py::arg("in_norm"), py::arg("post_norm"), py::arg("final_norm"), py::arg("lm_head"), py::arg("k_caches"),
            py::arg("v_caches"), py::arg("cos_sin"), py::arg("hq"), py::arg("hkv"), py::arg("head_dim"),
            py::arg("eps"), py::arg("scale"), py::arg("vocab_size"), py::arg("vocab_start"),
            py::arg("process_group"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0,
-           py::arg("qkv_b") = py::none())
+           py::arg("qkv_b") = py::none(), py::arg("windows") = py::none())
       .def("forward", &LlamaRunner::forward, py::call_guard<py::gil_scoped_release>());
   py::class_<BertRunner>(m, "BertRunner")
       .def(py::init<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<std::vector<at::Tensor>>,

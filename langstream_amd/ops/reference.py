@@ -189,9 +189,20 @@ def dequant_kv(K, V, k_scale=1.0, v_scale=1.0):
     return K, V
 
 
-def attention(q, k, v, scale, causal_offset: int | None):
+def _check_window(window) -> int:
+    window = int(window)
+    if window < 0:
+        raise ValueError(f"attention window must be >= 0 (0: no window), got {window}")
+    return window
+
+
+def attention(q, k, v, scale, causal_offset: int | None, window: int = 0, q_pos=None):
     """q [Tq, Hq, D], k/v [Tk, Hkv, D] -> [Tq, Hq, D]; causal if offset given
-    (query i sits at absolute position offset + i)."""
+    (query i sits at absolute position offset + i).  window > 0 (sliding-window attention):
+    the query at position p also sees no key at or below p - window, i.e. the window keys
+    p - window < j <= p; its position is offset + i, or q_pos [Tq] where the call is not
+    causal (decode: the one query sits at the last key)."""
+    window = _check_window(window)
     Hq, Hkv = q.shape[1], k.shape[1]
     G = Hq // Hkv
     kf = k.float().repeat_interleave(G, dim=1)
@@ -201,11 +212,20 @@ def attention(q, k, v, scale, causal_offset: int | None):
         qi = torch.arange(q.shape[0], device=q.device)[:, None] + causal_offset
         ki = torch.arange(k.shape[0], device=q.device)[None, :]
         s = s.masked_fill((ki > qi)[None], float("-inf"))
+    if window > 0:
+        if q_pos is None:
+            if causal_offset is None:
+                raise ValueError("a windowed attention needs the query positions")
+            q_pos = torch.arange(q.shape[0], device=q.device) + causal_offset
+        ki = torch.arange(k.shape[0], device=q.device)[None, :]
+        s = s.masked_fill((ki <= q_pos[:, None] - window)[None], float("-inf"))
     p = torch.softmax(s, dim=-1)
     return torch.einsum("hqk,khd->qhd", p, vf).to(q.dtype)
 
 
-def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale, k_scale=1.0, v_scale=1.0):
+def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale, k_scale=1.0, v_scale=1.0,
+                           window: int = 0):
+    window = _check_window(window)
     B = q.shape[0]
     D = k_cache.shape[3]
     qv = q.reshape(B, -1, D)
@@ -216,12 +236,14 @@ def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale, k
             outs.append(torch.zeros_like(qv[b: b + 1]))
             continue
         K, V = dequant_kv(*gather_kv(k_cache, v_cache, block_tables[b], n), k_scale, v_scale)
-        outs.append(attention(qv[b: b + 1], K, V, scale, causal_offset=None))
+        outs.append(attention(qv[b: b + 1], K, V, scale, causal_offset=None, window=window,
+                              q_pos=torch.tensor([n - 1], device=q.device)))
     return torch.cat(outs, 0)
 
 
 def paged_prefill_attention(q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, Hq, scale, k_scale=1.0,
-                            v_scale=1.0):
+                            v_scale=1.0, window: int = 0):
+    window = _check_window(window)
     D = k_cache.shape[3]
     T = q.shape[0]
     out = torch.empty(T, Hq, D, dtype=q.dtype, device=q.device)
@@ -229,7 +251,7 @@ def paged_prefill_attention(q, k_cache, v_cache, block_tables, q_start, q_len, c
         qs, ql, cl = int(q_start[s]), int(q_len[s]), int(ctx_len[s])
         K, V = dequant_kv(*gather_kv(k_cache, v_cache, block_tables[s], cl), k_scale, v_scale)
         qq = q[qs: qs + ql, : Hq * D].reshape(ql, Hq, D)
-        out[qs: qs + ql] = attention(qq, K, V, scale, causal_offset=cl - ql)
+        out[qs: qs + ql] = attention(qq, K, V, scale, causal_offset=cl - ql, window=window)
     return out.reshape(T, Hq * D)
 
 

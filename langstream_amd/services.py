@@ -18,6 +18,10 @@ Configuration (``local-gpu-configuration`` resource):
   max-model-len (4096), max-prefill-tokens (16384), kv-fraction (0.55), use-graphs (true),
   kv-cache-dtype (auto | bf16 | fp8; unset: the LS_KV_CACHE_DTYPE environment variable, else auto),
   kv-k-scale / kv-v-scale (1.0; the two scalars of an fp8 KV cache),
+  sliding-window (true | false; unset: the LS_SLIDING_WINDOW environment variable, else false.
+  A model-path with an active sliding window, Mistral or Qwen2 with use_sliding_window: true
+  serves every position with windowed attention in the layers that have a window, false only
+  the positions up to the window, with full attention),
   weights-path / embeddings-weights-path (optional safetensors with our packed layout),
   model-path (a Hugging Face directory: config.json, *.safetensors, tokenizer.json; llama /
   mistral / qwen2; the model's shape, weights and tokenizer come from it and it serves every
@@ -135,7 +139,10 @@ class ServiceRegistry:
             device = c.get("device") or default_device()
             if model_path:
                 from .models.loader import hf_model_type, llama_config_from_hf
-                mcfg = llama_config_from_hf(model_path)
+                sw = c.get("sliding-window")
+                if sw is None or sw == "":
+                    sw = os.environ.get("LS_SLIDING_WINDOW") or "false"
+                mcfg = llama_config_from_hf(model_path, sliding_window=str(sw).lower() in ("1", "true", "yes"))
                 template = template or ("chatml" if hf_model_type(model_path) == "qwen2" else "llama3")
             else:
                 mcfg = PRESETS[name]

@@ -65,6 +65,9 @@ def main():
                          "(paged_decode_attention_rope over an un-rotated qkv buffer, as the engine runs it)")
     ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="KV cache element type: fp8 = e4m3 codes of the same randn values (1 byte per element)")
+    ap.add_argument("--window", type=int, default=0,
+                    help="sliding-window attention: each row sees its last WINDOW keys only (0: no window); "
+                         "vis_TBps counts the visible KV bytes")
     a = ap.parse_args()
     Hq, Hkv, D = 32, 8, 128
     dev, bf = "cuda", torch.bfloat16
@@ -139,12 +142,12 @@ def main():
             it[0] += 1
             if a.rope:
                 ops.hip().paged_decode_attention_rope(o, qkv, pos, cos_sin, slots, k_, v_, bt, cl, scale, nsplit,
-                                                      mbps, ws)
+                                                      mbps, ws, a.window)
             else:
-                ops.hip().paged_decode_attention(o, q, k_, v_, bt, cl, scale, nsplit, mbps, ws)
+                ops.hip().paged_decode_attention(o, q, k_, v_, bt, cl, scale, nsplit, mbps, ws, window=a.window)
         us = timeit(call)
         if not a.rope:
-            ops.hip().paged_decode_attention(o, q, kc, vc, bt, cl, scale, nsplit, mbps, ws)
+            ops.hip().paged_decode_attention(o, q, kc, vc, bt, cl, scale, nsplit, mbps, ws, window=a.window)
         byts = int(ctxs.sum()) * Hkv * D * 2 * esz
         rec = {"B": B, "ctx": ctx, "us": round(us, 2), "TBps": round(byts / us / 1e6, 2),
                "kernel": "decode_attn_kernel", "wpp": os.environ.get("LS_ATTN_WPP", "auto"),
@@ -152,10 +155,13 @@ def main():
                "ragged": a.ragged, "pool_gb": a.pool_gb, "ring": a.ring, "rope": a.rope,
                "uniform_lo": a.uniform_lo, "sorted": a.sorted, "seq_blocks": a.seq_blocks,
                "shared_first": a.shared_first, "nt": os.environ.get("LS_ATTN_NT", "2"),
-               "interleave_gemm": a.interleave_gemm, "kv_dtype": a.kv_dtype}
+               "interleave_gemm": a.interleave_gemm, "kv_dtype": a.kv_dtype, "window": a.window}
+        if a.window > 0:
+            vis = int(ctxs.clamp(max=a.window).sum()) * Hkv * D * 2 * esz
+            rec["vis_TBps"] = round(vis / us / 1e6, 2)
         if not a.rope and (B <= 16 or (a.check_all and B * ctx <= 512 * 1024)) and a.pool_gb == 0:
             exp = ref.paged_decode_attention(q.float().cpu().reshape(B, Hq, D), kc.float().cpu(), vc.float().cpu(),
-                                             bt.cpu(), cl.cpu(), scale).reshape(B, Hq * D)   # over the dequantised cache
+                                             bt.cpu(), cl.cpu(), scale, window=a.window).reshape(B, Hq * D)   # over the dequantised cache
             rec["max_err"] = round(float((o.float().cpu() - exp).abs().max()), 4)
         print(json.dumps(rec), flush=True)
 
