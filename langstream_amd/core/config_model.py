@@ -332,10 +332,10 @@ RESOURCE_MODELS: Dict[str, Model] = {
         "model": S("Chat/completion model config name."), "embeddings-model": S("Embedding model config name."),
         "checkpoint": S("Safetensors checkpoint directory."),
         "model-path": S("Hugging Face model directory (config.json, *.safetensors, tokenizer.json) of a llama, "
-                        "mistral or qwen2 model: shape, weights and tokenizer come from it, and it serves every "
-                        "local chat and text completion."),
-        "chat-template": S("Chat prompt format: llama3 or chatml; unset: chatml for a qwen2 model-path, else "
-                           "llama3."),
+                        "mistral, qwen2 or qwen3 model: shape, weights and tokenizer come from it, and it serves "
+                        "every local chat and text completion."),
+        "chat-template": S("Chat prompt format: llama3 or chatml; unset: chatml for a qwen2 or qwen3 model-path, "
+                           "else llama3."),
         "tp": I("Tensor-parallel degree."),
         "max-batch": I("Max concurrent sequences."), "max-seq-len": I("Max sequence length."),
         "kv-cache-dtype": S("Paged KV cache element type: auto (the model dtype), bf16 or fp8 (e4m3, twice the "

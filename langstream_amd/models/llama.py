@@ -48,6 +48,9 @@ class LlamaConfig:
     bos_token_id: int = 128000
     eos_token_ids: tuple = (128001, 128009)
     qkv_bias: bool = False   # a bias on the fused QKV projection (Qwen2), added before RoPE
+    # a per-head RMSNorm (eps rms_eps) of every q and k head after the projection and before
+    # RoPE (Qwen3): one [head_dim] weight for all q heads and one for all k heads, per layer
+    qk_norm: bool = False
     # sliding-window attention (Mistral, Qwen2): a windowed layer's query at position p sees the
     # keys p - W < j <= p.  0: full attention.  window_layers: the windowed layer indices,
     # None with a window: every layer
@@ -70,6 +73,8 @@ class LlamaConfig:
         mlp = 3 * H * Fi
         if self.qkv_bias:
             qkv += (self.num_heads + 2 * self.num_kv_heads) * self.head_dim
+        if self.qk_norm:
+            qkv += 2 * self.head_dim
         return L * (qkv + o + mlp + 2 * H) + V * H * (1 if self.tie_embeddings else 2) + H
 
     def flops_per_token(self, ctx: int = 0) -> float:
@@ -102,6 +107,23 @@ PRESETS = {
     "qwen2-small": LlamaConfig(name="qwen2-small", vocab_size=32000, hidden_size=1024, intermediate_size=2816,
                                num_layers=4, num_heads=8, num_kv_heads=2, head_dim=128, max_position=4096,
                                bos_token_id=1, eos_token_ids=(2,), qkv_bias=True, rope_theta=1e6, rms_eps=1e-6),
+    # Qwen3: no bias, a per-head RMSNorm of q and k.  qwen3-tiny is qwen2-tiny's shape;
+    # qwen3-small has the layer shape of Qwen3-0.6B, in which Hq * D = 2048 is not the hidden size
+    "qwen3-tiny": LlamaConfig(name="qwen3-tiny", vocab_size=512, hidden_size=256, intermediate_size=512,
+                              num_layers=2, num_heads=4, num_kv_heads=2, head_dim=64, max_position=2048,
+                              bos_token_id=1, eos_token_ids=(2,), qk_norm=True, rope_theta=1e6, rms_eps=1e-6),
+    "qwen3-small": LlamaConfig(name="qwen3-small", vocab_size=32000, hidden_size=1024, intermediate_size=3072,
+                               num_layers=4, num_heads=16, num_kv_heads=8, head_dim=128, max_position=4096,
+                               bos_token_id=1, eos_token_ids=(2,), qk_norm=True, rope_theta=1e6, rms_eps=1e-6,
+                               tie_embeddings=True),
+    "qwen3-0.6b": LlamaConfig(name="qwen3-0.6b", vocab_size=151936, hidden_size=1024, intermediate_size=3072,
+                              num_layers=28, num_heads=16, num_kv_heads=8, head_dim=128, max_position=40960,
+                              bos_token_id=151643, eos_token_ids=(151645, 151643), qk_norm=True, rope_theta=1e6,
+                              rms_eps=1e-6, tie_embeddings=True),
+    "qwen3-8b": LlamaConfig(name="qwen3-8b", vocab_size=151936, hidden_size=4096, intermediate_size=12288,
+                            num_layers=36, num_heads=32, num_kv_heads=8, head_dim=128, max_position=40960,
+                            bos_token_id=151643, eos_token_ids=(151645, 151643), qk_norm=True, rope_theta=1e6,
+                            rms_eps=1e-6),
 }
 
 
@@ -198,9 +220,17 @@ class LlamaLayer:
         # packed like the rows of qkv_w: q heads, k heads, v heads
         self.qkv_b = torch.zeros((self.hq + 2 * self.hkv) * D, device=device, dtype=dtype) if cfg.qkv_bias else None
 
+        # one weight for all q heads and one for all k heads (replicated on every TP rank)
+        self.q_norm = torch.ones(D, device=device, dtype=dtype) if cfg.qk_norm else None
+        self.k_norm = torch.ones(D, device=device, dtype=dtype) if cfg.qk_norm else None
+
     def tensors(self):
         t = [self.qkv_w, self.o_w, self.gate_up_w, self.down_w, self.in_norm, self.post_norm]
-        return t + [self.qkv_b] if self.qkv_b is not None else t
+        if self.qkv_b is not None:
+            t.append(self.qkv_b)
+        if self.q_norm is not None:
+            t += [self.q_norm, self.k_norm]
+        return t
 
 
 class LlamaModel:
@@ -236,7 +266,11 @@ class LlamaModel:
     # ------------------------------------------------------------------ weights io
     def _layer_names(self) -> tuple:
         names = ("qkv_w", "o_w", "gate_up_w", "down_w", "in_norm", "post_norm")
-        return names + ("qkv_b",) if self.cfg.qkv_bias else names
+        if self.cfg.qkv_bias:
+            names += ("qkv_b",)
+        if self.cfg.qk_norm:
+            names += ("q_norm", "k_norm")
+        return names
 
     def state_dict(self) -> dict:
         sd = {"embed": self.embed, "final_norm": self.final_norm, "lm_head": self.lm_head}
@@ -279,7 +313,8 @@ class LlamaModel:
             kc, vc = kv_caches[li]
             qkv = _linear(x, layer.qkv_w)
             ops.rope_and_cache(qkv, meta.positions, self.cos_sin, meta.slots, kc, vc, self.hq, self.hkv,
-                               k_scale=ks, v_scale=vs, bias=layer.qkv_b)
+                               k_scale=ks, v_scale=vs, bias=layer.qkv_b, q_norm=layer.q_norm, k_norm=layer.k_norm,
+                               norm_eps=eps)
             q = qkv[:, : self.hq * D]
             nd = meta.num_decode
             win = cfg.layer_window(li)
@@ -329,7 +364,9 @@ class LlamaModel:
             self.lm_head, [kv[0] for kv in kv_caches], [kv[1] for kv in kv_caches], self.cos_sin, self.hq,
             self.hkv, self.cfg.head_dim, self.cfg.rms_eps, self.scale, self.cfg.vocab_size, self.vocab_start, pg,
             self.kv_k_scale, self.kv_v_scale, [l.qkv_b for l in L] if self.cfg.qkv_bias else None,
-            [self.cfg.layer_window(i) for i in range(len(L))])
+            [self.cfg.layer_window(i) for i in range(len(L))],
+            [l.q_norm for l in L] if self.cfg.qk_norm else None,
+            [l.k_norm for l in L] if self.cfg.qk_norm else None)
         self._runner = (key, runner, kv_caches)
         return runner
 

@@ -62,7 +62,7 @@ def load_packed(path: str, device="cpu") -> Dict[str, torch.Tensor]:
 # ---------------------------------------------------------------- Llama
 
 
-HF_MODEL_TYPES = ("llama", "mistral", "qwen2")   # Llama-architecture families the engine serves
+HF_MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")   # Llama-architecture families the engine serves
 
 
 def hf_model_type(model_dir: str) -> str:
@@ -108,14 +108,14 @@ LAYER_TYPES = ("full_attention", "sliding_attention")
 def _window_layers_from_hf(c: dict, mtype: str) -> Optional[tuple]:
     """The windowed layer indices of a checkpoint with an active sliding window, None for
     every layer: ``layer_types`` where the config has it, else the family's rule (Mistral:
-    every layer; Qwen2: the layers ``i >= max_window_layers``)."""
+    every layer; Qwen2 and Qwen3: the layers ``i >= max_window_layers``)."""
     n = int(c["num_hidden_layers"])
     lt = c.get("layer_types")
     if isinstance(lt, (list, tuple)) and lt:
         if len(lt) != n:
             raise ValueError(f"layer_types has {len(lt)} entries for {n} layers")
         layers = tuple(i for i, t in enumerate(lt) if t == "sliding_attention")
-    elif mtype == "qwen2":
+    elif mtype in ("qwen2", "qwen3"):
         layers = tuple(range(min(int(c.get("max_window_layers", 28)), n), n))
     else:
         return None
@@ -123,12 +123,16 @@ def _window_layers_from_hf(c: dict, mtype: str) -> Optional[tuple]:
 
 
 def llama_config_from_hf(model_dir: str, sliding_window: bool = False) -> LlamaConfig:
-    """The shape of a Hugging Face ``llama`` / ``mistral`` / ``qwen2`` directory.  Anything
+    """The shape of a Hugging Face ``llama`` / ``mistral`` / ``qwen2`` / ``qwen3`` directory.  Anything
     the engine would compute differently from the checkpoint's own model is refused here
     (other model types, other RoPE scalings, other layer types) or in ``convert_hf_llama``
     (other tensors).
 
-    A checkpoint with an active sliding window (Mistral's ``sliding_window``, Qwen2 with
+    ``qkv_bias`` is set for ``qwen2`` and for any checkpoint with ``q_proj.bias`` (a ``qwen3``
+    one with ``attention_bias``); ``qk_norm`` for ``qwen3`` and for any checkpoint with
+    ``self_attn.q_norm.weight``.
+
+    A checkpoint with an active sliding window (Mistral's ``sliding_window``, Qwen2 / Qwen3 with
     ``use_sliding_window``) shorter than ``max_position_embeddings`` is served in one of two
     ways.  ``sliding_window=False`` (the default): as a full-attention model up to the
     window, ``max_position`` clamped to it.  ``True``: over its whole position range, with
@@ -140,7 +144,9 @@ def llama_config_from_hf(model_dir: str, sliding_window: bool = False) -> LlamaC
     if mtype not in HF_MODEL_TYPES:
         raise ValueError(f"unsupported model_type {mtype!r} (supported: {', '.join(HF_MODEL_TYPES)})")
     theta, scaling = _rope_from_hf(c)
-    qkv_bias = mtype == "qwen2" or any(n.endswith("self_attn.q_proj.bias") for n in _checkpoint_names(model_dir))
+    names = _checkpoint_names(model_dir)
+    qkv_bias = mtype == "qwen2" or any(n.endswith("self_attn.q_proj.bias") for n in names)
+    qk_norm = mtype == "qwen3" or any(n.endswith("self_attn.q_norm.weight") for n in names)
     max_pos = c.get("max_position_embeddings", 8192)
     for t in c.get("layer_types") or ():
         if t not in LAYER_TYPES:
@@ -148,7 +154,7 @@ def llama_config_from_hf(model_dir: str, sliding_window: bool = False) -> LlamaC
     # an active sliding window: full attention equals windowed attention up to the window,
     # so positions past it are not served
     window = c.get("sliding_window")
-    if mtype == "qwen2" and not c.get("use_sliding_window", False):
+    if mtype in ("qwen2", "qwen3") and not c.get("use_sliding_window", False):
         window = None
     if mtype == "llama":
         window = None
@@ -181,14 +187,17 @@ def llama_config_from_hf(model_dir: str, sliding_window: bool = False) -> LlamaC
         rope_theta=theta, rope_scaling=scaling,
         rms_eps=c.get("rms_norm_eps", 1e-5), max_position=max_pos,
         tie_embeddings=bool(c.get("tie_word_embeddings", False)), bos_token_id=1 if bos is None else bos,
-        eos_token_ids=tuple(eos), qkv_bias=qkv_bias, sliding_window=win, window_layers=win_layers)
+        eos_token_ids=tuple(eos), qkv_bias=qkv_bias, qk_norm=qk_norm, sliding_window=win,
+        window_layers=win_layers)
 
 
 def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = None) -> Dict[str, torch.Tensor]:
-    """HF ``LlamaForCausalLM`` / ``MistralForCausalLM`` / ``Qwen2ForCausalLM`` names -> packed
-    names (fused qkv / gate_up, ``q/k/v_proj.bias`` fused into ``qkv_b``).  A checkpoint is
-    loaded whole or refused: a tensor that is not consumed (``o_proj.bias``, ``q_norm``, ...)
-    raises ValueError naming it; ``rotary_emb.inv_freq`` is the only name skipped."""
+    """HF ``LlamaForCausalLM`` / ``MistralForCausalLM`` / ``Qwen2ForCausalLM`` /
+    ``Qwen3ForCausalLM`` names -> packed names (fused qkv / gate_up, ``q/k/v_proj.bias`` fused
+    into ``qkv_b``, ``self_attn.q_norm.weight`` / ``k_norm.weight`` as ``q_norm`` / ``k_norm``,
+    both or neither).  A checkpoint is loaded whole or refused: a tensor that is not consumed
+    (``o_proj.bias``, ``mlp.*.bias``, ...) raises ValueError naming it; ``rotary_emb.inv_freq``
+    is the only name skipped."""
     used = set()
 
     def take(name):
@@ -204,6 +213,13 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = N
         out[f"layers.{i}.qkv_w"] = torch.cat([take(n + ".weight") for n in qkv], 0)
         if any(n + ".bias" in hf for n in qkv):
             out[f"layers.{i}.qkv_b"] = torch.cat([take(n + ".bias") for n in qkv], 0)
+        qn, kn = p + "self_attn.q_norm.weight", p + "self_attn.k_norm.weight"
+        if qn in hf or kn in hf:
+            for n in (qn, kn):
+                if n not in hf:
+                    raise ValueError(f"checkpoint tensor {n!r} is missing: q_norm and k_norm come together")
+            out[f"layers.{i}.q_norm"] = take(qn)
+            out[f"layers.{i}.k_norm"] = take(kn)
         out[f"layers.{i}.o_w"] = take(p + "self_attn.o_proj.weight")
         out[f"layers.{i}.gate_up_w"] = torch.cat([take(p + "mlp.gate_proj.weight"), take(p + "mlp.up_proj.weight")], 0)
         out[f"layers.{i}.down_w"] = take(p + "mlp.down_proj.weight")
@@ -222,7 +238,8 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = N
 def shard_llama(sd: Dict[str, torch.Tensor], cfg: LlamaConfig, rank: int, world: int) -> Dict[str, torch.Tensor]:
     """Full packed state dict -> this TP rank's shard: column-parallel qkv / gate_up
     (by heads / by FFN columns), row-parallel o / down, vocab-parallel embed / lm_head
-    (padded to a multiple of ``world``), replicated norms."""
+    (padded to a multiple of ``world``), replicated norms (the per-head ``q_norm`` / ``k_norm``
+    included: every rank's heads share the one weight)."""
     if world == 1:
         return dict(sd)
     from .llama import tp_kv_heads

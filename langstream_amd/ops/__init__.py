@@ -236,13 +236,19 @@ def bias_gelu_(x: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
 
 # ---------------------------------------------------------------- rope / kv cache
 def rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq: int, Hkv: int, apply_rope: bool = True,
-                   k_scale: float = 1.0, v_scale: float = 1.0, bias: Optional[torch.Tensor] = None):
+                   k_scale: float = 1.0, v_scale: float = 1.0, bias: Optional[torch.Tensor] = None,
+                   q_norm: Optional[torch.Tensor] = None, k_norm: Optional[torch.Tensor] = None,
+                   norm_eps: float = 1e-6):
     """k_scale / v_scale: the scales of an fp8 cache (ignored by bf16 caches).  bias: the
-    QKV projection's bias [(Hq + 2 Hkv) D], added before the rotation (q, k and v)."""
+    QKV projection's bias [(Hq + 2 Hkv) D], added before the rotation (q, k and v).
+    q_norm / k_norm: the [D] weights of a per-head RMSNorm (eps norm_eps) of the q and the k
+    heads, after the bias and before the rotation (Qwen3); both or neither."""
     if _gpu(qkv):
-        hip().rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope, k_scale, v_scale, bias)
+        hip().rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope, k_scale, v_scale, bias,
+                             q_norm, k_norm, norm_eps)
     else:
-        ref.rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope, k_scale, v_scale, bias)
+        ref.rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope, k_scale, v_scale, bias,
+                           q_norm, k_norm, norm_eps)
 
 
 # ---------------------------------------------------------------- attention

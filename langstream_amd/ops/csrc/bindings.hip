@@ -13,7 +13,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // k_scale / v_scale: the per-engine scales of an fp8 (float8_e4m3fn) KV cache; bf16 caches ignore them
   m.def("rope_and_cache", &rope_and_cache, py::arg("qkv"), py::arg("pos"), py::arg("cos_sin"), py::arg("slots"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("Hq"), py::arg("Hkv"), py::arg("apply_rope"),
-        py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0, py::arg("bias") = py::none());
+        py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0, py::arg("bias") = py::none(),
+        py::arg("q_norm") = py::none(), py::arg("k_norm") = py::none(), py::arg("norm_eps") = 1e-6);
   m.def("paged_decode_attention", &paged_decode_attention, py::arg("out"), py::arg("q"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("block_tables"), py::arg("ctx_lens"), py::arg("scale"), py::arg("nsplit"),
         py::arg("blocks_per_split"), py::arg("workspace"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0,
@@ -74,7 +75,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_gemm_qkv_rope", &decode_gemm_qkv_rope, py::arg("qkv"), py::arg("x"), py::arg("w"),
         py::arg("workspace"), py::arg("pos"), py::arg("cos_sin"), py::arg("slots"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("Hq"), py::arg("Hkv"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0,
-        py::arg("bias") = py::none());
+        py::arg("bias") = py::none(), py::arg("q_norm") = py::none(), py::arg("k_norm") = py::none(),
+        py::arg("norm_eps") = 1e-6);
   m.def("decode_gemm_f32_supported", &decode_gemm_f32_supported);
   m.def("decode_gemm_f32", &decode_gemm_f32, py::arg("out"), py::arg("x"), py::arg("w"), py::arg("bn") = 0);
   m.def("decode_gemm_silu", &decode_gemm_silu, py::arg("out"), py::arg("x"), py::arg("w"), py::arg("workspace"),

@@ -801,10 +801,14 @@ void decode_gemm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspac
 // F8: e4m3 caches; K as two 4-byte stores, V as 1-byte stores at an 8-byte stride.
 // BIAS: the projection's bias (bf16 [(Hq + 2 Hkv) D], q / k / v heads in the packed order)
 // is added to the f32 sums before the rotation, for v heads too.
-template <int D, bool F8, bool BIAS>
+// NORM: the per-head RMSNorm of q and k heads (Qwen3; rope.hip has the math) on the f32
+// sums after the bias.  The 16 threads of a head are an aligned group of lanes, so the
+// mean of squares is an xor-shuffle over 16 lanes; v heads skip it.
+template <int D, bool F8, bool BIAS, bool NORM>
 __global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(const float* __restrict__ part, int S, int M, int N,
                                                                  bf16* __restrict__ out, int64_t ldo, KvWrite kw,
-                                                                 const bf16* __restrict__ bias) {
+                                                                 const bf16* __restrict__ bias, QkNorm nw) {
+  static_assert(!NORM || D == 128, "NORM: the shuffle below takes the 16 lanes of a head");
   constexpr int HALF = D / 2, G4 = HALF / 4;
   const int H = kw.Hq + 2 * kw.Hkv;
   const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -848,6 +852,27 @@ __global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(const float* __
       b[j] += (float)bb[j];
     }
   }
+  if constexpr (NORM) {
+    // tid = (m * H + hd) * G4 + c with G4 = 16 and M * H * G4 threads in all: the lanes of
+    // a head are aligned, all past the bounds test above or none, and hd is uniform over
+    // them, so every lane this shuffle reads is active
+    if (hd < kw.Hq + kw.Hkv) {
+      const bf16* w = hd < kw.Hq ? nw.q : nw.k;
+      const bf16x4 wa = *reinterpret_cast<const bf16x4*>(w + 4 * c);
+      const bf16x4 wb = *reinterpret_cast<const bf16x4*>(w + HALF + 4 * c);
+      float ss = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ss += a[j] * a[j] + b[j] * b[j];
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 16);
+      const float r = rsqrtf(ss * (1.f / D) + nw.eps);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        a[j] = a[j] * r * (float)wa[j];
+        b[j] = b[j] * r * (float)wb[j];
+      }
+    }
+  }
   qkv_finish<D, F8>(kw, f32x4{a[0], a[1], a[2], a[3]}, f32x4{b[0], b[1], b[2], b[3]}, 1.f, m, hd, c, out, ldo);
 }
 
@@ -855,7 +880,8 @@ __global__ void __launch_bounds__(256) splitk_reduce_rope_kernel(const float* __
 // written to the paged cache (the same contract as decode_gemm + rope_and_cache).
 void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor pos,
                           at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, int64_t Hq,
-                          int64_t Hkv, double k_scale, double v_scale, c10::optional<at::Tensor> bias) {
+                          int64_t Hkv, double k_scale, double v_scale, c10::optional<at::Tensor> bias,
+                          c10::optional<at::Tensor> q_norm, c10::optional<at::Tensor> k_norm, double norm_eps) {
   check_xw(x, w);
   const int M = (int)x.size(0), K = (int)x.size(1), N = (int)w.size(0);
   bool f8;
@@ -865,13 +891,15 @@ void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor
   TORCH_CHECK(N == (Hq + 2 * Hkv) * D && N % 128 == 0, "decode_gemm_qkv_rope: qkv width");
   TORCH_CHECK(qkv.scalar_type() == at::kBFloat16 && qkv.size(0) == M && qkv.size(1) == N && qkv.stride(1) == 1);
   const bf16* bp = qkv_bias_ptr("decode_gemm_qkv_rope", bias, qkv, N);
+  const QkNorm nw = qk_norm_args("decode_gemm_qkv_rope", q_norm, k_norm, norm_eps, qkv, D);
   const int bn = pick_bn(N), tiles = N / bn;
   // at most 4 K slices: the fused reduction reads every slab once more (qkv at M = 256:
   // 27.5 us with 4 slices vs 28.1 with the 5 pick_split chooses, profiles/dgemm_bench_r3b.log)
   const int S = std::min(4, pick_split(tiles, K, 4));
   if (S == 1 || D != 128) {
     decode_gemm(qkv, x, w, workspace, c10::nullopt, c10::nullopt, 1e-5, 0, 0);
-    rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, true, k_scale, v_scale, bias);
+    rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, true, k_scale, v_scale, bias, q_norm, k_norm,
+                   norm_eps);
     return;
   }
   TORCH_CHECK(workspace.scalar_type() == at::kFloat && workspace.numel() >= (int64_t)S * M * N,
@@ -883,14 +911,17 @@ void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor
   else
     dgemm_launch<128, EPI_PARTIAL>(S, tiles, st, x, w, M, N, K, nullptr, 0, part, 0, nullptr, nullptr, nullptr);
   const int64_t threads = (int64_t)M * (Hq + 2 * Hkv) * (D / 8);
-#define LAUNCH_RB(FF, BB)                                                                     \
-  splitk_reduce_rope_kernel<128, FF, BB><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>( \
-      part, S, M, N, (bf16*)qkv.data_ptr(), qkv.stride(0), kw, bp)
+#define LAUNCH_RN(FF, BB, NN)                                                                     \
+  splitk_reduce_rope_kernel<128, FF, BB, NN><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>( \
+      part, S, M, N, (bf16*)qkv.data_ptr(), qkv.stride(0), kw, bp, nw)
+#define LAUNCH_RB(FF, BB) \
+  if (nw.q) LAUNCH_RN(FF, BB, true); else LAUNCH_RN(FF, BB, false)
 #define LAUNCH_RR(FF) \
-  if (bp) LAUNCH_RB(FF, true); else LAUNCH_RB(FF, false)
+  if (bp) { LAUNCH_RB(FF, true); } else { LAUNCH_RB(FF, false); }
   if (f8) { LAUNCH_RR(true); } else { LAUNCH_RR(false); }
 #undef LAUNCH_RR
 #undef LAUNCH_RB
+#undef LAUNCH_RN
 }
 
 // f32 OUTPUT (the LM head: logits the sampler reads in f32): out[M, N] f32 contiguous =

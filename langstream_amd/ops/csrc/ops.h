@@ -65,6 +65,38 @@ inline const bf16* qkv_bias_ptr(const char* who, const c10::optional<at::Tensor>
   return reinterpret_cast<const bf16*>(b.data_ptr());
 }
 
+// ---------------------------------------------------------------------------- q / k norm
+// The optional per-head RMSNorm of the q and the k heads (Qwen3): one bf16 [D] weight
+// shared by all q heads and one by all k heads, applied in f32 over the head dimension
+// after the bias and before the rotation; v heads are not normed.  Both weights or neither.
+struct QkNorm {
+  const bf16* q = nullptr;   // nullptr: no norm
+  const bf16* k = nullptr;
+  float eps = 0.f;
+};
+inline QkNorm qk_norm_args(const char* who, const c10::optional<at::Tensor>& q_norm,
+                           const c10::optional<at::Tensor>& k_norm, double eps, const at::Tensor& qkv, int64_t D) {
+  QkNorm n;
+  TORCH_CHECK(q_norm.has_value() == k_norm.has_value(), who, ": q_norm and k_norm are given together or not at all");
+  if (!q_norm.has_value()) return n;
+  TORCH_CHECK(eps > 0.0, who, ": norm_eps must be positive with q_norm / k_norm");
+  const at::Tensor* ws[2] = {&*q_norm, &*k_norm};
+  const char* names[2] = {"q_norm", "k_norm"};
+  for (int i = 0; i < 2; ++i) {
+    const at::Tensor& w = *ws[i];
+    TORCH_CHECK(w.is_cuda() && w.device() == qkv.device(), who, ": ", names[i], " must be on the device of qkv");
+    TORCH_CHECK(w.scalar_type() == at::kBFloat16, who, ": ", names[i], " must be bf16");
+    TORCH_CHECK(w.is_contiguous(), who, ": ", names[i], " must be contiguous");
+    TORCH_CHECK(w.numel() == D, who, ": ", names[i], " has ", w.numel(), " elements, head_dim = ", D);
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(w.data_ptr()) & 15) == 0, who, ": ", names[i],
+                " must be 16-byte aligned");
+  }
+  n.q = reinterpret_cast<const bf16*>(q_norm->data_ptr());
+  n.k = reinterpret_cast<const bf16*>(k_norm->data_ptr());
+  n.eps = (float)eps;
+  return n;
+}
+
 // ---------------------------------------------------------------------------- norm.hip
 void rmsnorm(at::Tensor out, at::Tensor x, at::Tensor w, double eps);
 void fused_add_rmsnorm(at::Tensor x, at::Tensor residual, at::Tensor w, double eps);
@@ -80,7 +112,8 @@ void bias_gelu(at::Tensor x, c10::optional<at::Tensor> bias);
 // ---------------------------------------------------------------------------- rope.hip
 void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache,
                     at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope, double k_scale, double v_scale,
-                    c10::optional<at::Tensor> bias);
+                    c10::optional<at::Tensor> bias, c10::optional<at::Tensor> q_norm = c10::nullopt,
+                    c10::optional<at::Tensor> k_norm = c10::nullopt, double norm_eps = 1e-6);
 
 // ---------------------------------------------------------------- attention_decode.hip
 void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
@@ -195,7 +228,9 @@ void decode_gemm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspac
                  c10::optional<at::Tensor> norm_w, double eps, int64_t bn_force, int64_t splits_force);
 void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor pos,
                           at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache, at::Tensor v_cache, int64_t Hq,
-                          int64_t Hkv, double k_scale, double v_scale, c10::optional<at::Tensor> bias);
+                          int64_t Hkv, double k_scale, double v_scale, c10::optional<at::Tensor> bias,
+                          c10::optional<at::Tensor> q_norm = c10::nullopt,
+                          c10::optional<at::Tensor> k_norm = c10::nullopt, double norm_eps = 1e-6);
 bool decode_gemm_f32_supported(const at::Tensor& w, int64_t M);
 void decode_gemm_f32(at::Tensor out, at::Tensor x, at::Tensor w, int64_t bn_force);
 void decode_gemm_silu(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor workspace, at::Tensor tickets,

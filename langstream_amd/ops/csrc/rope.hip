@@ -38,9 +38,14 @@ constexpr int HG = 8;    // heads per rotate workgroup
 // gets it too, so the V branch then writes bf16(v + b) back into the row as well as into
 // the cache -- the cache holds the bf16 value of the row (kv_write.h) for all three parts
 // -- and does so for tokens that are not cached.
-template <int D, int TOK, bool F8, bool BIAS>
+// NORM: a per-head RMSNorm of the q and the k heads (Qwen3) after the bias and before the
+// rotation, all in f32: x * rsqrt(mean(x^2) + eps) * w[d], with one bf16 [D] weight for all
+// q heads (nw.q) and one for all k heads (nw.k).  A head's D values sit in VPH adjacent
+// lanes, 16 each, so the mean is a sum in registers and an xor-shuffle over that group.
+// V heads are not normed: the V branch is the same with and without NORM.
+template <int D, int TOK, bool F8, bool BIAS, bool NORM>
 __global__ void __launch_bounds__(256) rope_cache_kernel(bf16* __restrict__ qkv, KvWrite kw, int64_t T,
-                                                         int apply_rope, const bf16* __restrict__ bias) {
+                                                         int apply_rope, const bf16* __restrict__ bias, QkNorm nw) {
   constexpr int HALF = D / 2;
   constexpr int VPH = HALF / 8;  // 16-B vectors per half head
   const int Hq = kw.Hq, Hkv = kw.Hkv;
@@ -73,6 +78,27 @@ __global__ void __launch_bounds__(256) rope_cache_kernel(bf16* __restrict__ qkv,
         for (int j = 0; j < 8; ++j) {
           a[j] += ba[j];
           b[j] += bb[j];
+        }
+      }
+      if constexpr (NORM) {
+        // i = (tl * nh + head) * VPH + c and blockDim.x is a multiple of VPH, so the VPH
+        // lanes of a head are an aligned group of one wave; tasks is a multiple of VPH, so
+        // a group is wholly inside or wholly outside this loop and every lane the shuffle
+        // reads is active.
+        float wa[8], wb[8];
+        const bf16* w = is_k ? nw.k : nw.q;
+        unpack8(ld16(w + c * 8), wa);
+        unpack8(ld16(w + HALF + c * 8), wb);
+        float ss = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ss += a[j] * a[j] + b[j] * b[j];
+#pragma unroll
+        for (int o = VPH / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, VPH);
+        const float r = rsqrtf(ss * (1.f / D) + nw.eps);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          a[j] = a[j] * r * wa[j];
+          b[j] = b[j] * r * wb[j];
         }
       }
       if (apply_rope) {
@@ -118,7 +144,8 @@ __global__ void __launch_bounds__(256) rope_cache_kernel(bf16* __restrict__ qkv,
 
 void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tensor slots, at::Tensor k_cache,
                     at::Tensor v_cache, int64_t Hq, int64_t Hkv, bool apply_rope, double k_scale,
-                    double v_scale, c10::optional<at::Tensor> bias) {
+                    double v_scale, c10::optional<at::Tensor> bias, c10::optional<at::Tensor> q_norm,
+                    c10::optional<at::Tensor> k_norm, double norm_eps) {
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.is_contiguous());
   TORCH_CHECK(k_cache.dim() == 4, "k_cache [NB, Hkv, BS, D], v_cache [NB, Hkv, BS/8, D, 8]");
   const int D = k_cache.size(3);
@@ -129,16 +156,20 @@ void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tens
                                    k_scale, v_scale, &f8);
   TORCH_CHECK(pos.numel() == T && slots.numel() == T);
   const bf16* bp = qkv_bias_ptr("rope_and_cache", bias, qkv, (Hq + 2 * Hkv) * D);
+  const QkNorm nw = qk_norm_args("rope_and_cache", q_norm, k_norm, norm_eps, qkv, D);
   if (T == 0) return;
   auto stream = at::hip::getCurrentHIPStream();
   const int nq = (int)((Hq + HG - 1) / HG), nk = (int)((Hkv + HG - 1) / HG);
   const bool small = T <= SMALL_T;
   const int tok = small ? TOK_SMALL : TOK_LARGE;
   dim3 grid((unsigned)((T + tok - 1) / tok), nq + nk + (int)Hkv);
+#define LAUNCH_N(DD, TT, FF, BB, NN)                                                                     \
+  rope_cache_kernel<DD, TT, FF, BB, NN><<<grid, 256, 0, stream>>>((bf16*)qkv.data_ptr(), kw, T, apply_rope ? 1 : 0, \
+                                                                  bp, nw)
 #define LAUNCH_B(DD, TT, FF, BB) \
-  rope_cache_kernel<DD, TT, FF, BB><<<grid, 256, 0, stream>>>((bf16*)qkv.data_ptr(), kw, T, apply_rope ? 1 : 0, bp)
+  if (nw.q) LAUNCH_N(DD, TT, FF, BB, true); else LAUNCH_N(DD, TT, FF, BB, false)
 #define LAUNCH_F(DD, TT, FF) \
-  if (bp) LAUNCH_B(DD, TT, FF, true); else LAUNCH_B(DD, TT, FF, false)
+  if (bp) { LAUNCH_B(DD, TT, FF, true); } else { LAUNCH_B(DD, TT, FF, false); }
 #define LAUNCH(DD, TT) \
   if (f8) { LAUNCH_F(DD, TT, true); } else { LAUNCH_F(DD, TT, false); }
   if (D == 128) { if (small) { LAUNCH(128, TOK_SMALL); } else { LAUNCH(128, TOK_LARGE); } }
@@ -147,4 +178,5 @@ void rope_and_cache(at::Tensor qkv, at::Tensor pos, at::Tensor cos_sin, at::Tens
 #undef LAUNCH
 #undef LAUNCH_F
 #undef LAUNCH_B
+#undef LAUNCH_N
 }

@@ -97,7 +97,9 @@ class LlamaRunner {
               int64_t hkv, int64_t head_dim, double eps, double scale, int64_t vocab_size, int64_t vocab_start,
               py::object process_group, double k_scale = 1.0, double v_scale = 1.0,
               c10::optional<std::vector<at::Tensor>> qkv_b = c10::nullopt,
-              c10::optional<std::vector<int64_t>> windows = c10::nullopt)
+              c10::optional<std::vector<int64_t>> windows = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> q_norm = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> k_norm = c10::nullopt)
       : embed_(embed), qkv_w_(qkv_w), o_w_(o_w), gate_up_w_(gate_up_w), down_w_(down_w), in_norm_(in_norm),
         post_norm_(post_norm), final_norm_(final_norm), lm_head_(lm_head), kc_(k_caches), vc_(v_caches),
         cos_sin_(cos_sin), hq_(hq), hkv_(hkv), d_(head_dim), eps_(eps), scale_(scale), vocab_(vocab_size),
@@ -129,6 +131,17 @@ class LlamaRunner {
         window_[l] = (*windows)[l];
       }
     }
+    // per-head RMSNorm of q and k (Qwen3): one bf16 [D] weight each per layer, applied with
+    // eps by rope_and_cache / decode_gemm_qkv_rope; the mode follows the lists
+    const bool has_qn = q_norm.has_value() && !q_norm->empty(), has_kn = k_norm.has_value() && !k_norm->empty();
+    TORCH_CHECK(has_qn == has_kn, "LlamaRunner: q_norm and k_norm are given together or not at all");
+    if (has_qn) {
+      q_norm_ = *q_norm;
+      k_norm_ = *k_norm;
+      TORCH_CHECK(q_norm_.size() == L && k_norm_.size() == L, "LlamaRunner: one q_norm and one k_norm per layer");
+      for (size_t l = 0; l < L; ++l) qk_norm_args("LlamaRunner", q_norm_[l], k_norm_[l], eps, qkv_w_[l], head_dim);
+      qknorm_ = true;
+    }
     if (!process_group.is_none()) pg_ = py::cast<c10::intrusive_ptr<::c10d::ProcessGroup>>(process_group);
     // LS_ONESHOT_AR=1: decode-sized all-reduces (<= LS_ONESHOT_AR_MAX elements, default
     // 256 x 8192) through the one-shot IPC kernel (allreduce.hip) instead of RCCL.  Both
@@ -157,7 +170,7 @@ class LlamaRunner {
       }
       // the norm-deferred layer (forward_dgemm): combine-path splits must exist for qkv /
       // o / down, the head dim must be 128 (one head per 128-column tile)
-      bool fz = !pg_ && !f8_ && !bias_ && head_dim == 128 && fused_env();
+      bool fz = !pg_ && !f8_ && !bias_ && !qknorm_ && head_dim == 128 && fused_env();
       const int64_t H = embed_.size(1);
       for (size_t l = 0; l < L && fz; ++l) {
         const at::Tensor* ws[3] = {&qkv_w_[l], &o_w_[l], &down_w_[l]};
@@ -332,14 +345,15 @@ class LlamaRunner {
     // roped: RoPE + the K/V cache write already done by the qkv GEMM / GEMV
     auto attend = [&](int64_t l, const at::Tensor& qkv, bool roped) {
       at::Tensor attn = at::empty({T, hq_ * d_}, qkv.options());
-      if (!roped && decode_only && !f8_ && !bias_ && rope_fused()) {
+      if (!roped && decode_only && !f8_ && !bias_ && !qknorm_ && rope_fused()) {
         // decode-only step: RoPE + K/V cache write inside the attention kernel
         paged_decode_attention_rope(attn, qkv, pos, cos_sin_, slots, kc_[l], vc_[l], d_bt, d_ctx, scale_, nsplit,
                                     bps, ws, window_[l]);
         return attn;
       }
       if (!roped)
-        rope_and_cache(qkv, pos, cos_sin_, slots, kc_[l], vc_[l], hq_, hkv_, true, k_scale_, v_scale_, bias(l));
+        rope_and_cache(qkv, pos, cos_sin_, slots, kc_[l], vc_[l], hq_, hkv_, true, k_scale_, v_scale_, bias(l),
+                       q_norm(l), k_norm(l), eps_);
       at::Tensor q = qkv.narrow(1, 0, hq_ * d_);
       if (num_decode > 0)
         paged_decode_attention(attn.narrow(0, 0, num_decode), q.narrow(0, 0, num_decode), kc_[l], vc_[l], d_bt,
@@ -356,8 +370,9 @@ class LlamaRunner {
     // 3.48 ms per batch-1 step, the serial tail outweighs the launch it saves.)
     // (fp8 KV caches: the GEMV's qkv epilogue writes bf16 K/V, so the un-fused GEMVs below;
     // a qkv bias: gemv_qkv and the RoPE-in-attention kernel do not add one, so the plain
-    // GEMV followed by rope_and_cache with the bias)
-    bool fused = gv && !pg_ && !f8_ && !bias_;
+    // GEMV followed by rope_and_cache with the bias; a q / k norm likewise: a head spans
+    // several blocks of gemv_qkv)
+    bool fused = gv && !pg_ && !f8_ && !bias_ && !qknorm_;
     for (int64_t l = 0; l < L && fused; ++l)
       fused = gemv_supported(qkv_w_[l], false) && gemv_supported(o_w_[l], false) &&
               gemv_supported(gate_up_w_[l], true) && gemv_supported(down_w_[l], false);
@@ -408,7 +423,7 @@ class LlamaRunner {
         qkv = at::empty({T, qkv_w_[l].size(0)}, x.options());
         if (decode_only && qkv_rope_fused()) {
           decode_gemm_qkv_rope(qkv, x, qkv_w_[l], dg_ws_, pos, cos_sin_, slots, kc_[l], vc_[l], hq_, hkv_, k_scale_,
-                               v_scale_, bias(l));
+                               v_scale_, bias(l), q_norm(l), k_norm(l), eps_);
           roped = true;
         } else {
           decode_gemm(qkv, x, qkv_w_[l], dg_ws_, c10::nullopt, c10::nullopt, eps_, 0, 0);
@@ -533,7 +548,7 @@ class LlamaRunner {
     return on;
   }
   bool fused_ready(int64_t T) const {
-    return !bias_ && cnt_qkv_.defined() && dgemm_enabled() && T >= std::max(dgemm_min_t(), fused_min_t()) &&
+    return !bias_ && !qknorm_ && cnt_qkv_.defined() && dgemm_enabled() && T >= std::max(dgemm_min_t(), fused_min_t()) &&
            T <= kDgemmMaxM;
   }
 
@@ -731,6 +746,14 @@ class LlamaRunner {
   std::vector<int64_t> window_;     // per-layer attention window, 0: full attention
   c10::optional<at::Tensor> bias(int64_t l) const {
     return bias_ ? c10::optional<at::Tensor>(qkv_b_[l]) : c10::nullopt;
+  }
+  std::vector<at::Tensor> q_norm_, k_norm_;   // per-layer [D] weights of the q / k head norm, empty without
+  bool qknorm_ = false;
+  c10::optional<at::Tensor> q_norm(int64_t l) const {
+    return qknorm_ ? c10::optional<at::Tensor>(q_norm_[l]) : c10::nullopt;
+  }
+  c10::optional<at::Tensor> k_norm(int64_t l) const {
+    return qknorm_ ? c10::optional<at::Tensor>(k_norm_[l]) : c10::nullopt;
   }
   c10::intrusive_ptr<::c10d::ProcessGroup> pg_;
 };
@@ -1354,13 +1377,15 @@ void bind_runners(py::module_& m) {
                     std::vector<at::Tensor>, std::vector<at::Tensor>, std::vector<at::Tensor>, at::Tensor, at::Tensor,
                     std::vector<at::Tensor>, std::vector<at::Tensor>, at::Tensor, int64_t, int64_t, int64_t, double,
                     double, int64_t, int64_t, py::object, double, double,
-                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<int64_t>>>(),
+                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<int64_t>>,
+                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>>(),
            py::arg("embed"), py::arg("qkv_w"), py::arg("o_w"), py::arg("gate_up_w"), py::arg("down_w"),
            py::arg("in_norm"), py::arg("post_norm"), py::arg("final_norm"), py::arg("lm_head"), py::arg("k_caches"),
            py::arg("v_caches"), py::arg("cos_sin"), py::arg("hq"), py::arg("hkv"), py::arg("head_dim"),
            py::arg("eps"), py::arg("scale"), py::arg("vocab_size"), py::arg("vocab_start"),
            py::arg("process_group"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0,
-           py::arg("qkv_b") = py::none(), py::arg("windows") = py::none())
+           py::arg("qkv_b") = py::none(), py::arg("windows") = py::none(),
+           py::arg("q_norm") = py::none(), py::arg("k_norm") = py::none())
       .def("forward", &LlamaRunner::forward, py::call_guard<py::gil_scoped_release>());
   py::class_<BertRunner>(m, "BertRunner")
       .def(py::init<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<std::vector<at::Tensor>>,

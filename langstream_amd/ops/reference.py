@@ -138,17 +138,28 @@ def apply_rope(x, pos, cos_sin):
 
 
 def rope_and_cache(qkv, pos, cos_sin, slots, k_cache, v_cache, Hq, Hkv, apply_rope_flag=True, k_scale=1.0,
-                   v_scale=1.0, bias=None):
+                   v_scale=1.0, bias=None, q_norm=None, k_norm=None, norm_eps=1e-6):
     """bias: [(Hq + 2 Hkv) D] in the packed order q, k, v heads (a QKV projection with bias),
-    added in f32 before the rotation, to v heads too; the row is rounded once."""
+    added in f32 before the rotation, to v heads too; the row is rounded once.
+    q_norm / k_norm: [D] weights of a per-head RMSNorm over the head dimension (Qwen3), in
+    f32 after the bias and before the rotation: x * rsqrt(mean(x^2) + norm_eps) * w, q_norm
+    for every q head and k_norm for every k head; v heads are not normed.  Both or neither."""
     assert k_cache.dtype == v_cache.dtype, "K and V caches of one dtype"
+    assert (q_norm is None) == (k_norm is None), "q_norm and k_norm are given together or not at all"
     f8 = is_fp8(k_cache)
     T = qkv.shape[0]
     D = k_cache.shape[3]
     BS = k_cache.shape[2]
     v = qkv.view(T, Hq + 2 * Hkv, D)
-    if bias is not None:
-        vf = v.float() + bias.float().view(Hq + 2 * Hkv, D)
+    if bias is not None or q_norm is not None:
+        vf = v.float()
+        if bias is not None:
+            vf = vf + bias.float().view(Hq + 2 * Hkv, D)
+        if q_norm is not None:
+            assert norm_eps > 0 and q_norm.numel() == D and k_norm.numel() == D
+            qk = vf[:, : Hq + Hkv]
+            w = torch.cat([q_norm.float().view(1, D).expand(Hq, D), k_norm.float().view(1, D).expand(Hkv, D)], 0)
+            vf[:, : Hq + Hkv] = qk * torch.rsqrt(qk.pow(2).mean(-1, keepdim=True) + norm_eps) * w
         if apply_rope_flag:
             vf[:, : Hq + Hkv] = apply_rope(vf[:, : Hq + Hkv], pos, cos_sin)
         v.copy_(vf)

@@ -24,9 +24,9 @@ Configuration (``local-gpu-configuration`` resource):
   the positions up to the window, with full attention),
   weights-path / embeddings-weights-path (optional safetensors with our packed layout),
   model-path (a Hugging Face directory: config.json, *.safetensors, tokenizer.json; llama /
-  mistral / qwen2; the model's shape, weights and tokenizer come from it and it serves every
+  mistral / qwen2 / qwen3; the model's shape, weights and tokenizer come from it and it serves every
   local completion, like force-chat-model), chat-template (llama3 | chatml; default chatml
-  for a qwen2 model-path, llama3 otherwise).
+  for a qwen2 or qwen3 model-path, llama3 otherwise).
 """
 from __future__ import annotations
 
@@ -143,7 +143,8 @@ class ServiceRegistry:
                 if sw is None or sw == "":
                     sw = os.environ.get("LS_SLIDING_WINDOW") or "false"
                 mcfg = llama_config_from_hf(model_path, sliding_window=str(sw).lower() in ("1", "true", "yes"))
-                template = template or ("chatml" if hf_model_type(model_path) == "qwen2" else "llama3")
+                template = template or ("chatml" if hf_model_type(model_path) in ("qwen2", "qwen3")
+                                        else "llama3")
             else:
                 mcfg = PRESETS[name]
             dtype = torch.bfloat16 if device.startswith("cuda") else torch.float32
