@@ -889,7 +889,10 @@ void decode_gemm_qkv_rope(at::Tensor qkv, at::Tensor x, at::Tensor w, at::Tensor
                                    k_scale, v_scale, &f8);
   const int D = (int)k_cache.size(3);
   TORCH_CHECK(N == (Hq + 2 * Hkv) * D && N % 128 == 0, "decode_gemm_qkv_rope: qkv width");
-  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16 && qkv.size(0) == M && qkv.size(1) == N && qkv.stride(1) == 1);
+  // contiguous: with one K split (or D != 128) the call goes through rope_and_cache, which
+  // takes no row stride (the one caller, LlamaRunner, allocates qkv itself)
+  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16 && qkv.size(0) == M && qkv.size(1) == N && qkv.is_contiguous(),
+              "decode_gemm_qkv_rope: qkv must be a contiguous bf16 [M, (Hq + 2 Hkv) D]");
   const bf16* bp = qkv_bias_ptr("decode_gemm_qkv_rope", bias, qkv, N);
   const QkNorm nw = qk_norm_args("decode_gemm_qkv_rope", q_norm, k_norm, norm_eps, qkv, D);
   const int bn = pick_bn(N), tiles = N / bn;
