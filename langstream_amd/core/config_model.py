@@ -340,6 +340,10 @@ RESOURCE_MODELS: Dict[str, Model] = {
         "max-batch": I("Max concurrent sequences."), "max-seq-len": I("Max sequence length."),
         "kv-cache-dtype": S("Paged KV cache element type: auto (the model dtype), bf16 or fp8 (e4m3, twice the "
                             "tokens per kv-fraction); unset: the LS_KV_CACHE_DTYPE environment variable, else auto."),
+        "weights-dtype": S("Element type of the four projection weights of every layer: auto (what the checkpoint "
+                           "holds; bf16 for presets), bf16 or fp8 (e4m3 codes with one scale per output row, "
+                           "activations stay bf16; a bf16 checkpoint or preset is quantised at load; bf16 on an "
+                           "fp8 checkpoint is refused); unset: the LS_WEIGHTS_DTYPE environment variable, else auto."),
         "sliding-window": B("Serve a model-path with an active sliding window (Mistral, Qwen2 with "
                             "use_sliding_window) over its whole position range, with windowed attention in the "
                             "layers that have a window; false serves only the positions up to the window, with "

@@ -247,6 +247,8 @@ class LLMEngine:
                       "decode_tokens": 0, "preemptions": 0, "requests": 0, "finished": 0, "graph_steps": 0,
                       "host_ms": 0.0, "wait_ms": 0.0, "launch_ms": 0.0, "retire_ms": 0.0, "prefix_hit_tokens": 0,
                       "prompt_tokens": 0, "kv_cache_dtype": self.kv_cache_dtype,
+                      "weights_dtype": getattr(model, "weights_dtype", "bf16"),
+                      "weight_bytes": int(getattr(model, "weight_bytes", 0)),
                       "kv_bytes_per_block": self.kv_bytes_per_block,
                       "sliding_window": int(getattr(model.cfg, "sliding_window", 0) or 0)}
         # prompt lengths of the most recent requests (decode attention cost follows the longest context)

@@ -186,8 +186,16 @@ def _pgemm(x: torch.Tensor, w: torch.Tensor, silu: bool) -> bool:
             and x.stride(-1) == 1 and ops.hip().gemm_prefill_supported(w, silu))
 
 
-def _linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+def _linear(x: torch.Tensor, w: torch.Tensor, s: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x . w^T; with row scales ``s`` the weight is fp8 codes and the W8A16 projection runs
+    (ops.linear_w8: the HIP kernels on the GPU, ops.reference.linear_w8 on the CPU)."""
+    if s is not None:
+        return ops.linear_w8(x, w, s)
     return ops.gemm_prefill(x, w) if _pgemm(x, w, False) else F.linear(x, w)
+
+
+WEIGHTS_DTYPES = ("bf16", "fp8")
+W8_NAMES = ("qkv", "o", "gate_up", "down")   # the projections an fp8 model stores as codes + row scales
 
 
 def tp_kv_heads(num_kv_heads: int, world: int) -> int:
@@ -202,7 +210,7 @@ def tp_kv_heads(num_kv_heads: int, world: int) -> int:
 
 
 class LlamaLayer:
-    def __init__(self, cfg: LlamaConfig, tp: TPInfo, device, dtype):
+    def __init__(self, cfg: LlamaConfig, tp: TPInfo, device, dtype, fp8: bool = False):
         H, D = cfg.hidden_size, cfg.head_dim
         assert cfg.num_heads % tp.world == 0, "TP must divide the query heads"
         assert cfg.intermediate_size % tp.world == 0
@@ -215,6 +223,14 @@ class LlamaLayer:
         self.o_w = mk(H, self.hq * D) / math.sqrt(2 * cfg.num_layers)
         self.gate_up_w = mk(2 * self.f, H)
         self.down_w = mk(H, self.f) / math.sqrt(2 * cfg.num_layers)
+        # fp8 weights: codes + one f32 scale per output row, quantised here, layer by layer,
+        # so the model never exists in full at the wider type
+        self.qkv_s = self.o_s = self.gate_up_s = self.down_s = None
+        if fp8:
+            for n in W8_NAMES:
+                codes, sc = ref.quantize_weight_fp8(getattr(self, n + "_w"))
+                setattr(self, n + "_w", codes)
+                setattr(self, n + "_s", sc)
         self.in_norm = torch.ones(H, device=device, dtype=dtype)
         self.post_norm = torch.ones(H, device=device, dtype=dtype)
         # packed like the rows of qkv_w: q heads, k heads, v heads
@@ -226,6 +242,8 @@ class LlamaLayer:
 
     def tensors(self):
         t = [self.qkv_w, self.o_w, self.gate_up_w, self.down_w, self.in_norm, self.post_norm]
+        if self.qkv_s is not None:
+            t += [self.qkv_s, self.o_s, self.gate_up_s, self.down_s]
         if self.qkv_b is not None:
             t.append(self.qkv_b)
         if self.q_norm is not None:
@@ -237,7 +255,12 @@ class LlamaModel:
     """Random-init (or state-dict-loaded) Llama weights + forward over the paged KV cache."""
 
     def __init__(self, cfg: LlamaConfig, device="cuda", dtype=torch.bfloat16, tp: Optional[TPInfo] = None,
-                 seed: int = 0):
+                 seed: int = 0, weights_dtype: str = "bf16"):
+        if weights_dtype not in WEIGHTS_DTYPES:
+            raise ValueError(f"weights_dtype must be one of {WEIGHTS_DTYPES}, got {weights_dtype!r}")
+        # "fp8": the four projections of every layer are float8_e4m3fn codes with one f32 scale
+        # per output row (W8A16: activations, embed, lm_head and the norms keep `dtype`)
+        self.weights_dtype = weights_dtype
         self.cfg = cfg
         self.device = torch.device(device)
         self.dtype = dtype
@@ -250,7 +273,8 @@ class LlamaModel:
             self.vocab_per_rank = (cfg.vocab_size + self.tp.world - 1) // self.tp.world
             self.vocab_start = self.tp.rank * self.vocab_per_rank
             self.embed = (torch.randn(self.vocab_per_rank, H, device=self.device) * 0.02).to(dtype)
-            self.layers = [LlamaLayer(cfg, self.tp, self.device, dtype) for _ in range(cfg.num_layers)]
+            self.layers = [LlamaLayer(cfg, self.tp, self.device, dtype, fp8=weights_dtype == "fp8")
+                           for _ in range(cfg.num_layers)]
             self.final_norm = torch.ones(H, device=self.device, dtype=dtype)
             self.lm_head = self.embed if cfg.tie_embeddings else (
                 torch.randn(self.vocab_per_rank, H, device=self.device) * 0.02).to(dtype)
@@ -262,6 +286,22 @@ class LlamaModel:
         # scales of an fp8 KV cache (the engine that owns the caches sets them; bf16 caches ignore them)
         self.kv_k_scale = 1.0
         self.kv_v_scale = 1.0
+        if weights_dtype == "fp8" and self.device.type == "cuda":
+            # a projection the W8 kernels do not take is refused here, by name, never rerouted
+            for i, l in enumerate(self.layers):
+                for n in W8_NAMES:
+                    w = getattr(l, n + "_w")
+                    if w.shape[0] % 64 or w.shape[1] % 64:
+                        raise ValueError(f"layers.{i}.{n}_w {tuple(w.shape)}: fp8 weights need both dimensions "
+                                         f"to be multiples of 64")
+
+    @property
+    def weight_bytes(self) -> int:
+        """Bytes of this rank's weights (tied lm_head counted once)."""
+        ts = [self.embed, self.final_norm] + ([] if self.lm_head is self.embed else [self.lm_head])
+        for l in self.layers:
+            ts += l.tensors()
+        return int(sum(t.numel() * t.element_size() for t in ts))
 
     # ------------------------------------------------------------------ weights io
     def _layer_names(self) -> tuple:
@@ -270,6 +310,8 @@ class LlamaModel:
             names += ("qkv_b",)
         if self.cfg.qk_norm:
             names += ("q_norm", "k_norm")
+        if self.weights_dtype == "fp8":
+            names += tuple(n + "_s" for n in W8_NAMES)
         return names
 
     def state_dict(self) -> dict:
@@ -286,9 +328,34 @@ class LlamaModel:
         self.final_norm.copy_(sd["final_norm"])
         if not self.cfg.tie_embeddings:
             self.lm_head.copy_(sd["lm_head"])
+        fp8 = self.weights_dtype == "fp8"
         for i, l in enumerate(self.layers):
             for n in self._layer_names():
-                getattr(l, n).copy_(sd[f"layers.{i}.{n}"])
+                key = f"layers.{i}.{n}"
+                if fp8 and n.endswith("_s"):
+                    continue   # loaded with its weight below
+                src = sd[key]
+                if n.endswith("_w") and n[:-2] in W8_NAMES:
+                    if not fp8 and ref.is_fp8(src):
+                        raise ValueError(f"{key} holds float8_e4m3fn codes but the model's weights_dtype is "
+                                         f"'bf16'; build the model with weights_dtype='fp8'")
+                    if fp8:
+                        skey = f"layers.{i}.{n[:-2]}_s"
+                        if ref.is_fp8(src):
+                            if skey not in sd:
+                                raise ValueError(f"{key} holds float8_e4m3fn codes but {skey} is missing")
+                            sc = sd[skey].to(torch.float32).reshape(-1)
+                            if sc.numel() == 1:
+                                sc = sc.expand(src.shape[0])
+                            if sc.numel() != src.shape[0]:
+                                raise ValueError(f"{skey} has {sc.numel()} elements for {src.shape[0]} rows")
+                            codes = src
+                        else:   # a wider tensor: quantise it with the one rule
+                            codes, sc = ref.quantize_weight_fp8(src.to(self.device))
+                        getattr(l, n).view(torch.uint8).copy_(codes.contiguous().view(torch.uint8))
+                        getattr(l, n[:-2] + "_s").copy_(sc)
+                        continue
+                getattr(l, n).copy_(src)
 
     # ------------------------------------------------------------------ forward
     def embed_tokens(self, ids: torch.Tensor) -> torch.Tensor:
@@ -311,7 +378,7 @@ class LlamaModel:
         ks, vs = self.kv_k_scale, self.kv_v_scale
         for li, layer in enumerate(self.layers):
             kc, vc = kv_caches[li]
-            qkv = _linear(x, layer.qkv_w)
+            qkv = _linear(x, layer.qkv_w, layer.qkv_s)
             ops.rope_and_cache(qkv, meta.positions, self.cos_sin, meta.slots, kc, vc, self.hq, self.hkv,
                                k_scale=ks, v_scale=vs, bias=layer.qkv_b, q_norm=layer.q_norm, k_norm=layer.k_norm,
                                norm_eps=eps)
@@ -332,14 +399,16 @@ class LlamaModel:
                 ops.paged_prefill_attention(q, kc, vc, meta.p_block_tables, meta.q_start, meta.q_len, meta.ctx_len,
                                             meta.tiles, self.hq, self.scale, out=attn, k_scale=ks, v_scale=vs,
                                             window=win)
-            o = _linear(attn, layer.o_w)
+            o = _linear(attn, layer.o_w, layer.o_s)
             self.tp.all_reduce(o)
             ops.fused_add_rmsnorm(o, residual, layer.post_norm, eps)
-            if _pgemm(o, layer.gate_up_w, True):
+            if layer.gate_up_s is not None:
+                a = ops.silu_and_mul(_linear(o, layer.gate_up_w, layer.gate_up_s))
+            elif _pgemm(o, layer.gate_up_w, True):
                 a = ops.gemm_prefill(o, layer.gate_up_w, silu=True)
             else:
                 a = ops.silu_and_mul(F.linear(o, layer.gate_up_w))
-            d = _linear(a, layer.down_w)
+            d = _linear(a, layer.down_w, layer.down_s)
             self.tp.all_reduce(d)
             nxt = self.layers[li + 1].in_norm if li + 1 < len(self.layers) else self.final_norm
             ops.fused_add_rmsnorm(d, residual, nxt, eps)
@@ -366,7 +435,8 @@ class LlamaModel:
             self.kv_k_scale, self.kv_v_scale, [l.qkv_b for l in L] if self.cfg.qkv_bias else None,
             [self.cfg.layer_window(i) for i in range(len(L))],
             [l.q_norm for l in L] if self.cfg.qk_norm else None,
-            [l.k_norm for l in L] if self.cfg.qk_norm else None)
+            [l.k_norm for l in L] if self.cfg.qk_norm else None,
+            *([[getattr(l, n + "_s") for l in L] for n in W8_NAMES] if self.weights_dtype == "fp8" else []))
         self._runner = (key, runner, kv_caches)
         return runner
 

@@ -13,12 +13,16 @@ from __future__ import annotations
 
 import glob
 import json
+import logging
 import os
 from typing import Dict, Iterable, Optional, Tuple
 
 import torch
 
-from .llama import LlamaConfig
+from .llama import LlamaConfig, W8_NAMES
+
+log = logging.getLogger(__name__)
+FP8 = torch.float8_e4m3fn
 
 # ---------------------------------------------------------------- safetensors IO
 
@@ -105,6 +109,34 @@ def _rope_from_hf(c: dict) -> Tuple[float, Optional[dict]]:
 LAYER_TYPES = ("full_attention", "sliding_attention")
 
 
+def _check_quantization_config(c: dict, names: set) -> None:
+    """``quantization_config`` is read only to refuse what is known not to fit the W8A16 path
+    (per-tensor or per-channel e4m3 weights, bf16 activations, bf16 lm_head); what the
+    checkpoint holds is decided by tensor names and dtypes in ``convert_hf_llama``.  The
+    field names follow the compressed-tensors and fbgemm_fp8 layouts."""
+    q = c.get("quantization_config")
+    if any(n.startswith("lm_head.weight_scale") for n in names):
+        raise ValueError("quantization_config: the checkpoint quantises lm_head (lm_head.weight_scale); only "
+                         "the layer projections may be fp8 (lm_head belongs in ignore / modules_to_not_convert)")
+    if not isinstance(q, dict):
+        return
+    if q.get("weight_block_size"):
+        raise ValueError(f"quantization_config.weight_block_size = {q['weight_block_size']!r}: block-wise "
+                         f"weight scales are not supported (per-tensor or per-channel only)")
+    if q.get("kv_cache_scheme") is not None:
+        raise ValueError("quantization_config.kv_cache_scheme is set: checkpoint KV-cache scales are not "
+                         "supported (the engine's own kv-cache-dtype option is)")
+    for gname, g in (q.get("config_groups") or {}).items():
+        w = (g or {}).get("weights") or {}
+        where = f"quantization_config.config_groups.{gname}.weights"
+        if w.get("num_bits", 8) != 8:
+            raise ValueError(f"{where}.num_bits = {w['num_bits']!r}: only 8-bit weights are supported")
+        if w.get("type", "float") != "float":
+            raise ValueError(f"{where}.type = {w['type']!r}: only float (e4m3) weights are supported")
+        if w.get("strategy", "tensor") not in ("tensor", "channel"):
+            raise ValueError(f"{where}.strategy = {w['strategy']!r}: only tensor and channel are supported")
+
+
 def _window_layers_from_hf(c: dict, mtype: str) -> Optional[tuple]:
     """The windowed layer indices of a checkpoint with an active sliding window, None for
     every layer: ``layer_types`` where the config has it, else the family's rule (Mistral:
@@ -145,6 +177,7 @@ def llama_config_from_hf(model_dir: str, sliding_window: bool = False) -> LlamaC
         raise ValueError(f"unsupported model_type {mtype!r} (supported: {', '.join(HF_MODEL_TYPES)})")
     theta, scaling = _rope_from_hf(c)
     names = _checkpoint_names(model_dir)
+    _check_quantization_config(c, names)
     qkv_bias = mtype == "qwen2" or any(n.endswith("self_attn.q_proj.bias") for n in names)
     qk_norm = mtype == "qwen3" or any(n.endswith("self_attn.q_norm.weight") for n in names)
     max_pos = c.get("max_position_embeddings", 8192)
@@ -199,18 +232,56 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = N
     (``o_proj.bias``, ``mlp.*.bias``, ...) raises ValueError naming it; ``rotary_emb.inv_freq``
     is the only name skipped."""
     used = set()
+    kinds = set()        # {"fp8", "wide"} over every projection: one kind per checkpoint
+    dropped = []         # activation-scale tensors consumed and not used
 
     def take(name):
         used.add(name)
         return hf[name]
 
+    def proj(name):
+        """(weight, f32 [N] scale or None) of one ``..._proj``: a float8_e4m3fn weight comes with a
+        sibling ``weight_scale`` (scalar, [1], [N] or [N, 1]; per-tensor scales are broadcast)."""
+        w = take(name + ".weight")
+        for extra in ("input_scale", "input_scale_ub"):
+            if name + "." + extra in hf:
+                dropped.append(name + "." + extra)
+                used.add(name + "." + extra)
+        if w.dtype != FP8:
+            kinds.add("wide")
+            return w, None
+        kinds.add("fp8")
+        sn = name + ".weight_scale"
+        if sn not in hf:
+            raise ValueError(f"checkpoint tensor {name + '.weight'!r} is float8_e4m3fn but {sn!r} is missing")
+        sc = take(sn).to(torch.float32).reshape(-1)
+        if sc.numel() == 1:
+            sc = sc.expand(w.shape[0])
+        if sc.numel() != w.shape[0]:
+            raise ValueError(f"checkpoint tensor {sn!r} has {sc.numel()} elements for {w.shape[0]} output rows "
+                             f"(per-tensor or per-channel scales only)")
+        if not bool((sc > 0).all()) or not bool(torch.isfinite(sc).all()):
+            raise ValueError(f"checkpoint tensor {sn!r} must be positive and finite")
+        return w, sc.contiguous()
+
+    def fuse(key, names):
+        ws, ss = zip(*[proj(n) for n in names])
+        if any(x is None for x in ss) != all(x is None for x in ss):
+            raise ValueError(f"checkpoint mixes fp8 and wider projections in {key} ({', '.join(names)})")
+        out[f"{key}_w"] = ws[0] if len(ws) == 1 else _cat_rows(ws)
+        if ss[0] is not None:
+            out[f"{key}_s"] = ss[0] if len(ss) == 1 else torch.cat(ss, 0)
+
     out = {"embed": take("model.embed_tokens.weight"), "final_norm": take("model.norm.weight")}
     out["lm_head"] = take("lm_head.weight") if "lm_head.weight" in hf else hf["model.embed_tokens.weight"]
+    for n in ("embed", "lm_head"):
+        if out[n].dtype == FP8:
+            raise ValueError(f"checkpoint tensor for {n} is float8_e4m3fn: only the layer projections may be fp8")
     i = 0
     while f"model.layers.{i}.self_attn.q_proj.weight" in hf:
         p = f"model.layers.{i}."
         qkv = [p + f"self_attn.{n}_proj" for n in "qkv"]
-        out[f"layers.{i}.qkv_w"] = torch.cat([take(n + ".weight") for n in qkv], 0)
+        fuse(f"layers.{i}.qkv", qkv)
         if any(n + ".bias" in hf for n in qkv):
             out[f"layers.{i}.qkv_b"] = torch.cat([take(n + ".bias") for n in qkv], 0)
         qn, kn = p + "self_attn.q_norm.weight", p + "self_attn.k_norm.weight"
@@ -220,14 +291,20 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = N
                     raise ValueError(f"checkpoint tensor {n!r} is missing: q_norm and k_norm come together")
             out[f"layers.{i}.q_norm"] = take(qn)
             out[f"layers.{i}.k_norm"] = take(kn)
-        out[f"layers.{i}.o_w"] = take(p + "self_attn.o_proj.weight")
-        out[f"layers.{i}.gate_up_w"] = torch.cat([take(p + "mlp.gate_proj.weight"), take(p + "mlp.up_proj.weight")], 0)
-        out[f"layers.{i}.down_w"] = take(p + "mlp.down_proj.weight")
+        fuse(f"layers.{i}.o", [p + "self_attn.o_proj"])
+        fuse(f"layers.{i}.gate_up", [p + "mlp.gate_proj", p + "mlp.up_proj"])
+        fuse(f"layers.{i}.down", [p + "mlp.down_proj"])
         out[f"layers.{i}.in_norm"] = take(p + "input_layernorm.weight")
         out[f"layers.{i}.post_norm"] = take(p + "post_attention_layernorm.weight")
         i += 1
     if cfg is not None:
         assert i == cfg.num_layers, f"checkpoint has {i} layers, config {cfg.num_layers}"
+    if len(kinds) > 1:
+        raise ValueError("checkpoint mixes fp8 (float8_e4m3fn) and wider projection weights; the projections "
+                         "of a checkpoint are all fp8 or all bf16 / f16 / f32")
+    if dropped:
+        log.info("fp8 checkpoint: %d activation-scale tensors (input_scale / input_scale_ub) dropped; "
+                 "activations stay bf16 (first: %s)", len(dropped), dropped[0])
     left = sorted(n for n in hf if n not in used and not n.endswith("rotary_emb.inv_freq"))
     if left:
         raise ValueError(f"checkpoint tensor {left[0]!r} is not supported"
@@ -235,11 +312,26 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = N
     return out
 
 
+def _cat_rows(ts) -> torch.Tensor:
+    """torch.cat along dim 0 that also takes float8 tensors (as bytes)."""
+    if ts[0].dtype == FP8:
+        return torch.cat([t.contiguous().view(torch.uint8) for t in ts], 0).view(FP8)
+    return torch.cat(list(ts), 0)
+
+
+def checkpoint_weights_dtype(sd: Dict[str, torch.Tensor]) -> str:
+    """"fp8" when the layer projections of a packed state dict are float8_e4m3fn codes, else "bf16"."""
+    keys = tuple(f".{n}_w" for n in W8_NAMES)
+    return "fp8" if any(k.endswith(keys) and v.dtype == FP8 for k, v in sd.items()) else "bf16"
+
+
 def shard_llama(sd: Dict[str, torch.Tensor], cfg: LlamaConfig, rank: int, world: int) -> Dict[str, torch.Tensor]:
     """Full packed state dict -> this TP rank's shard: column-parallel qkv / gate_up
     (by heads / by FFN columns), row-parallel o / down, vocab-parallel embed / lm_head
     (padded to a multiple of ``world``), replicated norms (the per-head ``q_norm`` / ``k_norm``
-    included: every rank's heads share the one weight)."""
+    included: every rank's heads share the one weight).  The row scales of fp8 weights follow
+    the rows: ``qkv_s`` / ``gate_up_s`` are sliced like ``qkv_w`` / ``gate_up_w``; ``o_s`` /
+    ``down_s`` are replicated (those weights are cut along K, every rank keeps all rows)."""
     if world == 1:
         return dict(sd)
     from .llama import tp_kv_heads
@@ -251,15 +343,15 @@ def shard_llama(sd: Dict[str, torch.Tensor], cfg: LlamaConfig, rank: int, world:
     vpr = (cfg.vocab_size + world - 1) // world
     out = {}
     for k, v in sd.items():
-        if k.endswith((".qkv_w", ".qkv_b")):   # the bias is sliced like the rows it belongs to
+        if k.endswith((".qkv_w", ".qkv_b", ".qkv_s")):   # bias and scales are sliced like the rows they belong to
             q, kk, vv = v[:Hq], v[Hq: Hq + Hkv], v[Hq + Hkv:]
-            out[k] = torch.cat([q[rank * hq * D:(rank + 1) * hq * D], kk[kv0 * D:(kv0 + hkv) * D],
-                                vv[kv0 * D:(kv0 + hkv) * D]], 0)
+            out[k] = _cat_rows([q[rank * hq * D:(rank + 1) * hq * D], kk[kv0 * D:(kv0 + hkv) * D],
+                                vv[kv0 * D:(kv0 + hkv) * D]])
         elif k.endswith(".o_w"):
             out[k] = v[:, rank * hq * D:(rank + 1) * hq * D]
-        elif k.endswith(".gate_up_w"):
+        elif k.endswith((".gate_up_w", ".gate_up_s")):
             g, u = v[:F], v[F:]
-            out[k] = torch.cat([g[rank * f:(rank + 1) * f], u[rank * f:(rank + 1) * f]], 0)
+            out[k] = _cat_rows([g[rank * f:(rank + 1) * f], u[rank * f:(rank + 1) * f]])
         elif k.endswith(".down_w"):
             out[k] = v[:, rank * f:(rank + 1) * f]
         elif k in ("embed", "lm_head"):

@@ -185,6 +185,44 @@ def gemm_fused(x, w, bias=None, gelu=False, residual=None, ln_stats_in=None, ln_
     return r
 
 
+_W8_WS: dict = {}
+
+
+def _w8_workspace(device, nbytes: int) -> torch.Tensor:
+    """The split-K workspace of w8_gemm for callers without one of their own: one f32 buffer
+    per device, grown on demand (the native runner owns a fixed one for graph capture)."""
+    ws = _W8_WS.get(device)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=device)
+        _W8_WS[device] = ws
+    return ws
+
+
+def linear_w8(x, w, s, out=None, splits: int = 0):
+    """W8A16 projection (ops/csrc/gemm_w8.hip): bf16((x . code^T) * s) for bf16 x [M, K],
+    float8_e4m3fn codes w [N, K] and f32 row scales s [N].  M <= 4 runs on w8_gemv where its
+    shape rule holds (K % 1024 == 0), everything else on w8_gemm; ``splits`` > 0 forces the
+    tiled kernel with that many K slices.  N % 64 == 0 and K % 64 == 0; anything else raises."""
+    if _gpu(x, w, s):
+        h = hip()
+        M, N, K = x.shape[0], w.shape[0], w.shape[1]
+        out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+        need = splits * M * N * 4 if splits > 0 else (h.w8_gemm_workspace(M, N, K) if N >= 64 and K >= 64 else 0)
+        h.linear_w8(out, x, w, s, _w8_workspace(x.device, need), splits)
+        return out
+    r = ref.linear_w8(x, w, s)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
+def w8_launch_counts(reset: bool = False) -> dict:
+    """Launches of the W8 kernels per variant since the last reset: {"gemv": n,
+    "gemm_bm64_s4": n, ...} (tile rows and K slices of w8_gemm)."""
+    return dict(hip().w8_launch_counts(reset))
+
+
 def gemm_prefill(x, w, silu=False, out=None, variant=-1):
     """Prefill-sized MFMA GEMM (ops/csrc/gemm_prefill.hip, 256 x 256 tiles): x . w^T, or with
     ``silu`` the Llama SwiGLU of the fused gate_up weight [2F, K]: silu(x.g^T) * (x.u^T).

@@ -88,5 +88,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_gemm_launch_counts", &decode_gemm_launch_counts, py::arg("reset") = false);
   m.def("rms_prep", &rms_prep);
   m.def("rows_rms_scale", &rows_rms_scale);
+  m.def("w8_supported", &w8_supported);
+  m.def("w8_gemv_supported", &w8_gemv_supported);
+  m.def("w8_gemm_workspace", &w8_gemm_workspace);
+  m.def("w8_gemm", &w8_gemm, py::arg("out"), py::arg("x"), py::arg("w"), py::arg("s"), py::arg("workspace"),
+        py::arg("splits") = 0);
+  m.def("w8_gemv", &w8_gemv);
+  m.def("linear_w8", &linear_w8, py::arg("out"), py::arg("x"), py::arg("w"), py::arg("s"), py::arg("workspace"),
+        py::arg("splits") = 0);
+  m.def("w8_launch_counts", &w8_launch_counts, py::arg("reset") = false);
   bind_runners(m);
 }

@@ -248,5 +248,15 @@ pybind11::dict decode_gemm_launch_counts(bool reset);
 void rms_prep(at::Tensor y, at::Tensor sumsq, at::Tensor h, at::Tensor g);
 void rows_rms_scale(at::Tensor out, at::Tensor y, at::Tensor sumsq, double eps);
 
+// ------------------------------------------------------------------------ gemm_w8.hip
+// W8A16 projections: e4m3fn weight codes [N, K] with one f32 scale per output row.
+bool w8_supported(const at::Tensor& w);
+bool w8_gemv_supported(const at::Tensor& w);
+int64_t w8_gemm_workspace(int64_t M, int64_t N, int64_t K);
+void w8_gemm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s, at::Tensor workspace, int64_t splits_force);
+void w8_gemv(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s);
+void linear_w8(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s, at::Tensor workspace, int64_t splits_force);
+pybind11::dict w8_launch_counts(bool reset);
+
 // -------------------------------------------------------------------------- runner.hip
 void bind_runners(pybind11::module_& m);

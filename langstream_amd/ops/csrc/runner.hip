@@ -99,7 +99,11 @@ class LlamaRunner {
               c10::optional<std::vector<at::Tensor>> qkv_b = c10::nullopt,
               c10::optional<std::vector<int64_t>> windows = c10::nullopt,
               c10::optional<std::vector<at::Tensor>> q_norm = c10::nullopt,
-              c10::optional<std::vector<at::Tensor>> k_norm = c10::nullopt)
+              c10::optional<std::vector<at::Tensor>> k_norm = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> qkv_s = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> o_s = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> gate_up_s = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> down_s = c10::nullopt)
       : embed_(embed), qkv_w_(qkv_w), o_w_(o_w), gate_up_w_(gate_up_w), down_w_(down_w), in_norm_(in_norm),
         post_norm_(post_norm), final_norm_(final_norm), lm_head_(lm_head), kc_(k_caches), vc_(v_caches),
         cos_sin_(cos_sin), hq_(hq), hkv_(hkv), d_(head_dim), eps_(eps), scale_(scale), vocab_(vocab_size),
@@ -142,6 +146,48 @@ class LlamaRunner {
       for (size_t l = 0; l < L; ++l) qk_norm_args("LlamaRunner", q_norm_[l], k_norm_[l], eps, qkv_w_[l], head_dim);
       qknorm_ = true;
     }
+    // fp8 (e4m3) projection weights (W8A16, gemm_w8.hip): the four per-layer lists of f32 row
+    // scales are given together or not at all; given means every projection is codes + scales
+    {
+      const c10::optional<std::vector<at::Tensor>>* sl[4] = {&qkv_s, &o_s, &gate_up_s, &down_s};
+      int given = 0;
+      for (auto* p : sl) given += p->has_value() && !(*p)->empty();
+      TORCH_CHECK(given == 0 || given == 4,
+                  "LlamaRunner: the weight scales qkv_s, o_s, gate_up_s and down_s are given together or not at all");
+      w8_ = given == 4;
+      const std::vector<at::Tensor>* wl[4] = {&qkv_w_, &o_w_, &gate_up_w_, &down_w_};
+      const char* names[4] = {"qkv_w", "o_w", "gate_up_w", "down_w"};
+      if (w8_) {
+        qkv_s_ = *qkv_s;
+        o_s_ = *o_s;
+        gate_up_s_ = *gate_up_s;
+        down_s_ = *down_s;
+        const std::vector<at::Tensor>* ss[4] = {&qkv_s_, &o_s_, &gate_up_s_, &down_s_};
+        int64_t wsz = 0;
+        for (int k = 0; k < 4; ++k) {
+          TORCH_CHECK(ss[k]->size() == L, "LlamaRunner: one ", names[k], " scale tensor per layer");
+          for (size_t l = 0; l < L; ++l) {
+            const at::Tensor& w = (*wl[k])[l];
+            const at::Tensor& sc = (*ss[k])[l];
+            TORCH_CHECK(w8_supported(w), "LlamaRunner: layers.", l, ".", names[k],
+                        " is not a contiguous float8_e4m3fn [N, K] with N % 64 == 0 and K % 64 == 0 (shape ",
+                        w.sizes(), ", ", w.scalar_type(), "): the W8 kernels do not take it");
+            TORCH_CHECK(sc.is_cuda() && sc.device() == w.device() && sc.scalar_type() == at::kFloat &&
+                            sc.is_contiguous() && sc.numel() == w.size(0),
+                        "LlamaRunner: the scale of layers.", l, ".", names[k], " must be a contiguous float32 [",
+                        w.size(0), "] on the device of the weight");
+            wsz = std::max(wsz, w8_gemm_workspace(int64_t(1) << 20, w.size(0), w.size(1)));
+          }
+        }
+        // split-K partials of w8_gemm, sized once for every row count so graph captures never allocate
+        w8_ws_ = at::empty({std::max<int64_t>(wsz / 4, 4)}, embed_.options().dtype(at::kFloat));
+      } else {
+        for (int k = 0; k < 4; ++k)
+          for (size_t l = 0; l < L; ++l)
+            TORCH_CHECK((*wl[k])[l].scalar_type() != at::kFloat8_e4m3fn, "LlamaRunner: layers.", l, ".", names[k],
+                        " holds float8_e4m3fn codes but no weight scales were given");
+      }
+    }
     if (!process_group.is_none()) pg_ = py::cast<c10::intrusive_ptr<::c10d::ProcessGroup>>(process_group);
     // LS_ONESHOT_AR=1: decode-sized all-reduces (<= LS_ONESHOT_AR_MAX elements, default
     // 256 x 8192) through the one-shot IPC kernel (allreduce.hip) instead of RCCL.  Both
@@ -156,7 +202,7 @@ class LlamaRunner {
     // largest decode batch so graph captures never allocate
     auto dev = embed_.options();
     status_ = at::zeros({4}, dev.dtype(at::kInt));
-    if (dgemm_enabled()) {
+    if (dgemm_enabled() && !w8_) {
       int64_t wsz = 1, fmax = 0;
       for (size_t l = 0; l < L; ++l) {
         const at::Tensor* ws[3] = {&qkv_w_[l], &o_w_[l], &down_w_[l]};
@@ -298,6 +344,14 @@ class LlamaRunner {
     return out;
   }
 
+  // bf16((x . code^T) * s) for any row count: w8_gemv at T <= 4 where its shape rule holds,
+  // else w8_gemm (gemm_w8.hip)
+  at::Tensor proj_w8(const at::Tensor& x, const at::Tensor& w, const at::Tensor& s) {
+    at::Tensor out = at::empty({x.size(0), w.size(0)}, x.options());
+    linear_w8(out, x, w, s, w8_ws_, 0);
+    return out;
+  }
+
   // silu(x . w[:F]^T) * (x . w[F:]^T) for any row count (same routing as proj)
   at::Tensor proj_silu(const at::Tensor& x, const at::Tensor& w) {
     const int64_t T = x.size(0);
@@ -345,7 +399,7 @@ class LlamaRunner {
     // roped: RoPE + the K/V cache write already done by the qkv GEMM / GEMV
     auto attend = [&](int64_t l, const at::Tensor& qkv, bool roped) {
       at::Tensor attn = at::empty({T, hq_ * d_}, qkv.options());
-      if (!roped && decode_only && !f8_ && !bias_ && !qknorm_ && rope_fused()) {
+      if (!roped && decode_only && !f8_ && !bias_ && !qknorm_ && !w8_ && rope_fused()) {
         // decode-only step: RoPE + K/V cache write inside the attention kernel
         paged_decode_attention_rope(attn, qkv, pos, cos_sin_, slots, kc_[l], vc_[l], d_bt, d_ctx, scale_, nsplit,
                                     bps, ws, window_[l]);
@@ -372,7 +426,7 @@ class LlamaRunner {
     // a qkv bias: gemv_qkv and the RoPE-in-attention kernel do not add one, so the plain
     // GEMV followed by rope_and_cache with the bias; a q / k norm likewise: a head spans
     // several blocks of gemv_qkv)
-    bool fused = gv && !pg_ && !f8_ && !bias_ && !qknorm_;
+    bool fused = gv && !pg_ && !f8_ && !bias_ && !qknorm_ && !w8_;
     for (int64_t l = 0; l < L && fused; ++l)
       fused = gemv_supported(qkv_w_[l], false) && gemv_supported(o_w_[l], false) &&
               gemv_supported(gate_up_w_[l], true) && gemv_supported(down_w_[l], false);
@@ -413,7 +467,23 @@ class LlamaRunner {
       fused_add_rmsnorm(dn, residual, final_norm_, eps_);
       x = dn;
     }
-    for (int64_t l = 0; l < L && !fused; ++l) {
+    // fp8 projection weights: the plain sequence on the W8 kernels (gemm_w8.hip) -- no fused
+    // GEMV layer, no RoPE inside the GEMM or the attention, no bf16 projection kernel
+    for (int64_t l = 0; l < L && w8_; ++l) {
+      at::Tensor qkv = proj_w8(x, qkv_w_[l], qkv_s_[l]);
+      at::Tensor attn = attend(l, qkv, false);
+      at::Tensor o = proj_w8(attn, o_w_[l], o_s_[l]);
+      all_reduce(o);
+      fused_add_rmsnorm(o, residual, post_norm_[l], eps_);
+      at::Tensor gu = proj_w8(o, gate_up_w_[l], gate_up_s_[l]);
+      at::Tensor a = at::empty({T, gate_up_w_[l].size(0) / 2}, o.options());
+      silu_and_mul(a, gu);
+      at::Tensor dn = proj_w8(a, down_w_[l], down_s_[l]);
+      all_reduce(dn);
+      fused_add_rmsnorm(dn, residual, l + 1 < L ? in_norm_[l + 1] : final_norm_, eps_);
+      x = dn;
+    }
+    for (int64_t l = 0; l < L && !fused && !w8_; ++l) {
       at::Tensor qkv;
       bool roped = false;   // RoPE + the K/V cache write already done by the qkv GEMM's reduction
       if (gv && gemv_supported(qkv_w_[l], false)) {
@@ -548,7 +618,7 @@ class LlamaRunner {
     return on;
   }
   bool fused_ready(int64_t T) const {
-    return !bias_ && !qknorm_ && cnt_qkv_.defined() && dgemm_enabled() && T >= std::max(dgemm_min_t(), fused_min_t()) &&
+    return !w8_ && !bias_ && !qknorm_ && cnt_qkv_.defined() && dgemm_enabled() && T >= std::max(dgemm_min_t(), fused_min_t()) &&
            T <= kDgemmMaxM;
   }
 
@@ -749,6 +819,9 @@ class LlamaRunner {
   }
   std::vector<at::Tensor> q_norm_, k_norm_;   // per-layer [D] weights of the q / k head norm, empty without
   bool qknorm_ = false;
+  std::vector<at::Tensor> qkv_s_, o_s_, gate_up_s_, down_s_;   // per-layer f32 row scales of fp8 weights, empty without
+  bool w8_ = false;            // the four projections of every layer are float8_e4m3fn codes + scales
+  at::Tensor w8_ws_;           // split-K workspace of w8_gemm
   c10::optional<at::Tensor> q_norm(int64_t l) const {
     return qknorm_ ? c10::optional<at::Tensor>(q_norm_[l]) : c10::nullopt;
   }
@@ -1378,6 +1451,8 @@ void bind_runners(py::module_& m) {
                     std::vector<at::Tensor>, std::vector<at::Tensor>, at::Tensor, int64_t, int64_t, int64_t, double,
                     double, int64_t, int64_t, py::object, double, double,
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<int64_t>>,
+                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
+                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>>(),
            py::arg("embed"), py::arg("qkv_w"), py::arg("o_w"), py::arg("gate_up_w"), py::arg("down_w"),
            py::arg("in_norm"), py::arg("post_norm"), py::arg("final_norm"), py::arg("lm_head"), py::arg("k_caches"),
@@ -1385,7 +1460,8 @@ void bind_runners(py::module_& m) {
            py::arg("eps"), py::arg("scale"), py::arg("vocab_size"), py::arg("vocab_start"),
            py::arg("process_group"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0,
            py::arg("qkv_b") = py::none(), py::arg("windows") = py::none(),
-           py::arg("q_norm") = py::none(), py::arg("k_norm") = py::none())
+           py::arg("q_norm") = py::none(), py::arg("k_norm") = py::none(), py::arg("qkv_s") = py::none(),
+           py::arg("o_s") = py::none(), py::arg("gate_up_s") = py::none(), py::arg("down_s") = py::none())
       .def("forward", &LlamaRunner::forward, py::call_guard<py::gil_scoped_release>());
   py::class_<BertRunner>(m, "BertRunner")
       .def(py::init<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<std::vector<at::Tensor>>,

@@ -35,6 +35,35 @@ def quantize_kv(x, scale: float = 1.0):
     return (x.float() * inv.to(x.device)).clamp(-FP8_MAX, FP8_MAX).to(FP8_DTYPE)
 
 
+# ---- fp8 projection weights (opt-in, W8A16).  A quantised projection is a pair: codes
+# float8_e4m3fn [N, K] and one positive f32 scale per output row s [N];
+#   y[m, n] = bf16((sum_k f32(x[m, k]) * f32(code[n, k])) * s[n])
+# with the scale applied once to the f32 sum.
+def quantize_weight_fp8(w):
+    """(codes, s) of a [N, K] weight (any float dtype): s[n] = max_k |w[n, k]| / 448 in f32
+    (1 for an all-zero row), code = e4m3fn(RNE(clamp(w / s, -448, 448)))."""
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    s = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax)).to(torch.float32)
+    codes = (wf / s[:, None]).clamp(-FP8_MAX, FP8_MAX).to(FP8_DTYPE)
+    return codes.contiguous(), s.contiguous()
+
+
+def dequantize_weight_fp8(codes, s, dtype=torch.float32):
+    """code * s as `dtype` (f32: exact up to one rounding of the product)."""
+    return (codes.to(dtype) * s.to(dtype)[:, None])
+
+
+def linear_w8(x, codes, s, dtype=None):
+    """The W8A16 projection on the CPU: (x . code^T) * s accumulated in f32 (or `dtype`,
+    e.g. float64 for an oracle); returns x's dtype for bf16 / f16 x, else the compute dtype."""
+    ct = dtype or torch.float32
+    y = (x.to(ct) @ codes.to(ct).t()) * s.to(ct)
+    if dtype is None and x.dtype in (torch.bfloat16, torch.float16):
+        return y.to(x.dtype)
+    return y
+
+
 def rmsnorm(x, w, eps):
     xf = x.float()
     return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * w.float()).to(x.dtype)

@@ -18,6 +18,10 @@ Configuration (``local-gpu-configuration`` resource):
   max-model-len (4096), max-prefill-tokens (16384), kv-fraction (0.55), use-graphs (true),
   kv-cache-dtype (auto | bf16 | fp8; unset: the LS_KV_CACHE_DTYPE environment variable, else auto),
   kv-k-scale / kv-v-scale (1.0; the two scalars of an fp8 KV cache),
+  weights-dtype (auto | bf16 | fp8; unset: the LS_WEIGHTS_DTYPE environment variable, else auto.
+  auto: what the checkpoint holds, bf16 for presets; fp8 on a bf16 checkpoint or preset quantises
+  the four projections of every layer at load, e4m3 codes with one scale per output row; bf16 on an
+  fp8 checkpoint is refused),
   sliding-window (true | false; unset: the LS_SLIDING_WINDOW environment variable, else false.
   A model-path with an active sliding window, Mistral or Qwen2 with use_sliding_window: true
   serves every position with windowed attention in the layers that have a window, false only
@@ -159,13 +163,26 @@ class ServiceRegistry:
                 if device.startswith("cuda") and not chk["graph"]:
                     c["use-graphs"] = "false"
             log.info("starting LLM engine %s on %s", name, device)
-            model_ = LlamaModel(mcfg, device=device, dtype=dtype, tp=self.tp)
+            wd = str(c.get("weights-dtype") or os.environ.get("LS_WEIGHTS_DTYPE") or "auto").lower()
+            if wd not in ("auto", "bf16", "fp8"):
+                raise ValueError(f"weights-dtype {wd!r}: expected auto, bf16 or fp8")
+            sd = None
             if model_path or c.get("weights-path"):
-                from .models.loader import load_packed, shard_llama
+                from .models.loader import checkpoint_weights_dtype, load_packed, shard_llama
                 sd = load_packed(model_path or c["weights-path"], device)
+                held = checkpoint_weights_dtype(sd)
+                if wd == "bf16" and held == "fp8":
+                    raise ValueError("weights-dtype bf16: the checkpoint holds fp8 (float8_e4m3fn) projection "
+                                     "weights, which are not widened; use auto or fp8")
+                wd = held if wd == "auto" else wd
                 if self.tp is not None and self.tp.world > 1:
                     sd = shard_llama(sd, mcfg, self.tp.rank, self.tp.world)
+            elif wd == "auto":
+                wd = "bf16"
+            model_ = LlamaModel(mcfg, device=device, dtype=dtype, tp=self.tp, weights_dtype=wd)
+            if sd is not None:
                 model_.load_state_dict(sd)
+                del sd
             tok_path = c.get("tokenizer-path")
             if not tok_path and model_path and os.path.exists(os.path.join(model_path, "tokenizer.json")):
                 tok_path = os.path.join(model_path, "tokenizer.json")

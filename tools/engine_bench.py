@@ -26,7 +26,7 @@ def bench_llm(args):
         import dataclasses
         cfg = dataclasses.replace(cfg, name=cfg.name + "+qkv-bias", qkv_bias=True)
     t0 = time.time()
-    model = LlamaModel(cfg, device="cuda")
+    model = LlamaModel(cfg, device="cuda", weights_dtype=args.weights_dtype)
     for layer in model.layers if args.qkv_bias else ():
         layer.qkv_b.normal_(0.0, 0.5)
     sync()
@@ -37,7 +37,8 @@ def bench_llm(args):
     eng.capture_graphs([b for b in eng.buckets if b <= args.batch])
     sync()
     print(json.dumps({"event": "graphs", "s": round(time.time() - t0, 2), "blocks": eng.num_blocks,
-                      "kv_cache_dtype": eng.kv_cache_dtype, "kv_bytes_per_block": eng.kv_bytes_per_block}), flush=True)
+                      "kv_cache_dtype": eng.kv_cache_dtype, "kv_bytes_per_block": eng.kv_bytes_per_block,
+                      "weights_dtype": eng.stats["weights_dtype"], "weight_bytes": eng.stats["weight_bytes"]}), flush=True)
     sp = SamplingParams(max_tokens=args.gen, temperature=0.8, top_p=0.95, ignore_eos=True)
     prompts = [[(i * 31 + j) % 1000 + 100 for j in range(args.prompt)] for i in range(args.batch)]
     # warmup
@@ -185,6 +186,8 @@ if __name__ == "__main__":
     ap.add_argument("--prefill-chunk", type=int, default=16384)
     ap.add_argument("--kv-dtype", choices=("auto", "bf16", "fp8"), default="auto",
                     help="KV cache element type of the LLM engine (LLMEngine kv_cache_dtype)")
+    ap.add_argument("--weights-dtype", choices=("bf16", "fp8"), default="bf16",
+                    help="LLM: element type of the layer projections (LlamaModel weights_dtype; fp8: W8A16 kernels)")
     ap.add_argument("--qkv-bias", action="store_true",
                     help="LLM: the model's shape with a random bias on the QKV projection (LlamaConfig.qkv_bias)")
     ap.add_argument("--texts", type=int, default=2048)
