@@ -96,13 +96,15 @@ def build_hip(verbose: bool = False) -> str:
         "-Wno-unused-result", "-Wno-deprecated-declarations", "-Wno-unused-command-line-argument",
         "-fgpu-rdc" if False else "-fno-gpu-rdc",
     ]
+    # per-source extras: gemm_w8a8.hip is compiled without the packed-f32 VALU forms
+    extra = {"gemm_w8a8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
     jobs = []
     objs = []
     for s in srcs:
         o = os.path.join(BUILD_DIR, os.path.basename(s) + ".o")
         objs.append(o)
         if not os.path.exists(o) or os.path.getmtime(o) < max(os.path.getmtime(s), hdr_time):
-            jobs.append([HIPCC, *cflags, *defs, *inc, "-I", CSRC, "-c", s, "-o", o])
+            jobs.append([HIPCC, *cflags, *extra.get(os.path.basename(s), []), *defs, *inc, "-I", CSRC, "-c", s, "-o", o])
     if jobs:
         with cf.ThreadPoolExecutor(_jobs()) as ex:
             list(ex.map(_run, jobs))

@@ -344,6 +344,10 @@ RESOURCE_MODELS: Dict[str, Model] = {
                            "holds; bf16 for presets), bf16 or fp8 (e4m3 codes with one scale per output row, "
                            "activations stay bf16; a bf16 checkpoint or preset is quantised at load; bf16 on an "
                            "fp8 checkpoint is refused); unset: the LS_WEIGHTS_DTYPE environment variable, else auto."),
+        "activations-dtype": S("Element type of the projection inputs: bf16, or fp8 (needs fp8 weights; steps of "
+                               "more than 4 rows quantise each projection's input rows to e4m3 with one dynamic "
+                               "scale per row and run on the FP8 matrix instructions); unset: the "
+                               "LS_ACTIVATIONS_DTYPE environment variable, else bf16."),
         "sliding-window": B("Serve a model-path with an active sliding window (Mistral, Qwen2 with "
                             "use_sliding_window) over its whole position range, with windowed attention in the "
                             "layers that have a window; false serves only the positions up to the window, with "

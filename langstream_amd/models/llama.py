@@ -186,15 +186,24 @@ def _pgemm(x: torch.Tensor, w: torch.Tensor, silu: bool) -> bool:
             and x.stride(-1) == 1 and ops.hip().gemm_prefill_supported(w, silu))
 
 
-def _linear(x: torch.Tensor, w: torch.Tensor, s: Optional[torch.Tensor] = None) -> torch.Tensor:
+def _a8(x: torch.Tensor, w: torch.Tensor, a8: bool) -> bool:
+    """The per-projection rule of fp8 activations (the one of runner.hip): more than 4 rows
+    and a weight the W8A8 kernels take; T <= 4 stays on the W8A16 GEMV, which is
+    bandwidth-bound on the weight bytes and gains nothing from FP8 activations."""
+    return a8 and x.shape[0] > 4 and ops.w8a8_supported(w)
+
+
+def _linear(x: torch.Tensor, w: torch.Tensor, s: Optional[torch.Tensor] = None, a8: bool = False) -> torch.Tensor:
     """x . w^T; with row scales ``s`` the weight is fp8 codes and the W8A16 projection runs
-    (ops.linear_w8: the HIP kernels on the GPU, ops.reference.linear_w8 on the CPU)."""
+    (ops.linear_w8: the HIP kernels on the GPU, ops.reference.linear_w8 on the CPU), or with
+    ``a8`` the W8A8 one where _a8 allows it (ops.linear_w8a8)."""
     if s is not None:
-        return ops.linear_w8(x, w, s)
+        return ops.linear_w8a8(x, w, s) if _a8(x, w, a8) else ops.linear_w8(x, w, s)
     return ops.gemm_prefill(x, w) if _pgemm(x, w, False) else F.linear(x, w)
 
 
 WEIGHTS_DTYPES = ("bf16", "fp8")
+ACTIVATIONS_DTYPES = ("bf16", "fp8")
 W8_NAMES = ("qkv", "o", "gate_up", "down")   # the projections an fp8 model stores as codes + row scales
 
 
@@ -255,9 +264,17 @@ class LlamaModel:
     """Random-init (or state-dict-loaded) Llama weights + forward over the paged KV cache."""
 
     def __init__(self, cfg: LlamaConfig, device="cuda", dtype=torch.bfloat16, tp: Optional[TPInfo] = None,
-                 seed: int = 0, weights_dtype: str = "bf16"):
+                 seed: int = 0, weights_dtype: str = "bf16", activations_dtype: str = "bf16"):
         if weights_dtype not in WEIGHTS_DTYPES:
             raise ValueError(f"weights_dtype must be one of {WEIGHTS_DTYPES}, got {weights_dtype!r}")
+        if activations_dtype not in ACTIVATIONS_DTYPES:
+            raise ValueError(f"activations_dtype must be one of {ACTIVATIONS_DTYPES}, got {activations_dtype!r}")
+        if activations_dtype == "fp8" and weights_dtype != "fp8":
+            raise ValueError("activations_dtype='fp8' needs weights_dtype='fp8': both operands go to the FP8 "
+                             "matrix unit")
+        # "fp8": steps of more than 4 rows quantise the input rows of every projection to e4m3
+        # with one dynamic f32 scale per row and run the W8A8 kernels (ops/csrc/gemm_w8a8.hip)
+        self.activations_dtype = activations_dtype
         # "fp8": the four projections of every layer are float8_e4m3fn codes with one f32 scale
         # per output row (W8A16: activations, embed, lm_head and the norms keep `dtype`)
         self.weights_dtype = weights_dtype
@@ -376,9 +393,10 @@ class LlamaModel:
         x = ops.rmsnorm(h, self.layers[0].in_norm, eps)
         D = cfg.head_dim
         ks, vs = self.kv_k_scale, self.kv_v_scale
+        a8 = self.activations_dtype == "fp8"
         for li, layer in enumerate(self.layers):
             kc, vc = kv_caches[li]
-            qkv = _linear(x, layer.qkv_w, layer.qkv_s)
+            qkv = _linear(x, layer.qkv_w, layer.qkv_s, a8)
             ops.rope_and_cache(qkv, meta.positions, self.cos_sin, meta.slots, kc, vc, self.hq, self.hkv,
                                k_scale=ks, v_scale=vs, bias=layer.qkv_b, q_norm=layer.q_norm, k_norm=layer.k_norm,
                                norm_eps=eps)
@@ -399,16 +417,23 @@ class LlamaModel:
                 ops.paged_prefill_attention(q, kc, vc, meta.p_block_tables, meta.q_start, meta.q_len, meta.ctx_len,
                                             meta.tiles, self.hq, self.scale, out=attn, k_scale=ks, v_scale=vs,
                                             window=win)
-            o = _linear(attn, layer.o_w, layer.o_s)
+            o = _linear(attn, layer.o_w, layer.o_s, a8)
             self.tp.all_reduce(o)
             ops.fused_add_rmsnorm(o, residual, layer.post_norm, eps)
             if layer.gate_up_s is not None:
-                a = ops.silu_and_mul(_linear(o, layer.gate_up_w, layer.gate_up_s))
+                gu = _linear(o, layer.gate_up_w, layer.gate_up_s, a8)
+                if _a8(gu, layer.down_w, a8):
+                    # the quantiser forms bf16(silu(g) * u) itself: no [T, F] intermediate
+                    d = ops.linear_w8a8(gu, layer.down_w, layer.down_s, silu_mul=True)
+                    a = None
+                else:
+                    a = ops.silu_and_mul(gu)
             elif _pgemm(o, layer.gate_up_w, True):
                 a = ops.gemm_prefill(o, layer.gate_up_w, silu=True)
             else:
                 a = ops.silu_and_mul(F.linear(o, layer.gate_up_w))
-            d = _linear(a, layer.down_w, layer.down_s)
+            if a is not None:
+                d = _linear(a, layer.down_w, layer.down_s, a8)
             self.tp.all_reduce(d)
             nxt = self.layers[li + 1].in_norm if li + 1 < len(self.layers) else self.final_norm
             ops.fused_add_rmsnorm(d, residual, nxt, eps)
@@ -436,7 +461,8 @@ class LlamaModel:
             [self.cfg.layer_window(i) for i in range(len(L))],
             [l.q_norm for l in L] if self.cfg.qk_norm else None,
             [l.k_norm for l in L] if self.cfg.qk_norm else None,
-            *([[getattr(l, n + "_s") for l in L] for n in W8_NAMES] if self.weights_dtype == "fp8" else []))
+            *([[getattr(l, n + "_s") for l in L] for n in W8_NAMES] if self.weights_dtype == "fp8" else []),
+            activations_fp8=self.activations_dtype == "fp8")
         self._runner = (key, runner, kv_caches)
         return runner
 

@@ -219,8 +219,67 @@ def linear_w8(x, w, s, out=None, splits: int = 0):
 
 def w8_launch_counts(reset: bool = False) -> dict:
     """Launches of the W8 kernels per variant since the last reset: {"gemv": n,
-    "gemm_bm64_s4": n, ...} (tile rows and K slices of w8_gemm)."""
+    "gemm_bm64_s4": n, ...} (tile rows and K slices of w8_gemm), and of the W8A8 kernels:
+    "a8_bm128_s2" (tile rows and K slices of w8a8_gemm), "quant", "quant_silu"."""
     return dict(hip().w8_launch_counts(reset))
+
+
+def quantize_rows_fp8(x, silu_mul: bool = False):
+    """Per-row dynamic FP8 quantisation (ops/csrc/gemm_w8a8.hip): bf16 x [M, K] -> (xq
+    float8_e4m3fn [M, K], xs f32 [M]) with xs = amax / 448 (1 for a zero row) and xq =
+    e4m3(clamp(x * (1 / xs))).  ``silu_mul``: x is gu [M, 2F] and bf16(silu(g) * u) is quantised."""
+    if _gpu(x):
+        K = x.shape[1] // 2 if silu_mul else x.shape[1]
+        xq = torch.empty(x.shape[0], K, dtype=ref.FP8_DTYPE, device=x.device)
+        xs = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        hip().quantize_rows_fp8(xq, xs, x, silu_mul)
+        return xq, xs
+    return ref.quantize_rows_fp8(x, silu_mul)
+
+
+def w8a8_gemm(xq, xs, w, ws, out=None, splits: int = 0):
+    """FP8 x FP8 GEMM on the gfx950 FP8 MFMA (ops/csrc/gemm_w8a8.hip): bf16((code_x . code_w^T)
+    * xs[m] * ws[n]) for codes xq [M, K], w [N, K] and f32 scales xs [M], ws [N].  N % 128 == 0
+    and K % 128 == 0; ``splits`` > 0 forces that many K slices (at most 16)."""
+    if _gpu(xq, w):
+        h = hip()
+        M, N, K = xq.shape[0], w.shape[0], w.shape[1]
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=xq.device) if out is None else out
+        need = splits * M * N * 4 if splits > 0 else (h.w8a8_gemm_workspace(M, N, K) if N >= 128 and K >= 128 else 0)
+        h.w8a8_gemm(out, xq, xs, w, ws, _w8_workspace(xq.device, need), splits)
+        return out
+    r = ref.w8a8_gemm(xq, xs, w, ws)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
+def linear_w8a8(x, w, ws, out=None, splits: int = 0, silu_mul: bool = False):
+    """W8A8 projection: quantize_rows_fp8(x), then w8a8_gemm with the weight codes w [N, K]
+    and their row scales ws [N]; bf16 [M, N].  ``silu_mul``: x is gu [M, 2K] and the rows
+    quantised are bf16(silu(g) * u), formed inside the quantiser."""
+    if _gpu(x, w, ws):
+        if silu_mul:
+            return w8a8_gemm(*quantize_rows_fp8(x, True), w, ws, out=out, splits=splits)
+        h = hip()
+        M, N, K = x.shape[0], w.shape[0], w.shape[1]
+        out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+        need = splits * M * N * 4 if splits > 0 else (h.w8a8_gemm_workspace(M, N, K) if N >= 128 and K >= 128 else 0)
+        h.linear_w8a8(out, x, w, ws, _w8_workspace(x.device, need), splits)
+        return out
+    r = ref.linear_w8a8(x, w, ws, silu_mul=silu_mul)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
+def w8a8_supported(w) -> bool:
+    """The shape rule of the W8A8 kernels: contiguous float8_e4m3fn [N, K], N % 128 == 0,
+    K % 128 == 0, K <= 28672 (the same rule on the CPU, so both paths route alike)."""
+    return (w.dim() == 2 and w.dtype == ref.FP8_DTYPE and w.is_contiguous() and w.shape[0] >= 128
+            and w.shape[0] % 128 == 0 and w.shape[1] >= 128 and w.shape[1] % 128 == 0 and w.shape[1] <= 28672)
 
 
 def gemm_prefill(x, w, silu=False, out=None, variant=-1):

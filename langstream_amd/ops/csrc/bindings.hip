@@ -97,5 +97,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_w8", &linear_w8, py::arg("out"), py::arg("x"), py::arg("w"), py::arg("s"), py::arg("workspace"),
         py::arg("splits") = 0);
   m.def("w8_launch_counts", &w8_launch_counts, py::arg("reset") = false);
+  m.def("w8a8_supported", &w8a8_supported);
+  m.def("w8a8_gemm_workspace", &w8a8_gemm_workspace);
+  m.def("quantize_rows_fp8", &quantize_rows_fp8, py::arg("xq"), py::arg("xs"), py::arg("x"),
+        py::arg("silu_mul") = false);
+  m.def("w8a8_gemm", &w8a8_gemm, py::arg("out"), py::arg("xq"), py::arg("xs"), py::arg("w"), py::arg("ws"),
+        py::arg("workspace"), py::arg("splits") = 0);
+  m.def("linear_w8a8", &linear_w8a8, py::arg("out"), py::arg("x"), py::arg("w"), py::arg("ws"), py::arg("workspace"),
+        py::arg("splits") = 0);
   bind_runners(m);
 }

@@ -408,5 +408,6 @@ pybind11::dict w8_launch_counts(bool reset) {
       if (n == 0) continue;
       d[pybind11::str("gemm_bm" + std::to_string(b ? 128 : 64) + "_s" + std::to_string(s))] = n;
     }
+  w8a8_launch_counts(d, reset);   // a8_bm{BM}_s{S}, quant, quant_silu (gemm_w8a8.hip)
   return d;
 }

@@ -258,5 +258,16 @@ void w8_gemv(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s);
 void linear_w8(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s, at::Tensor workspace, int64_t splits_force);
 pybind11::dict w8_launch_counts(bool reset);
 
+// ---------------------------------------------------------------------- gemm_w8a8.hip
+// W8A8 projections: per-row dynamic e4m3fn activation codes times the W8 weights on the FP8 MFMA.
+bool w8a8_supported(const at::Tensor& w);
+int64_t w8a8_gemm_workspace(int64_t M, int64_t N, int64_t K);
+void quantize_rows_fp8(at::Tensor xq, at::Tensor xs, at::Tensor x, bool silu_mul);
+void w8a8_gemm(at::Tensor out, at::Tensor xq, at::Tensor xs, at::Tensor w, at::Tensor ws, at::Tensor workspace,
+               int64_t splits_force);
+void linear_w8a8(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor ws, at::Tensor workspace,
+                 int64_t splits_force);
+void w8a8_launch_counts(pybind11::dict& d, bool reset);   // adds its keys to the census of w8_launch_counts
+
 // -------------------------------------------------------------------------- runner.hip
 void bind_runners(pybind11::module_& m);

@@ -103,7 +103,7 @@ class LlamaRunner {
               c10::optional<std::vector<at::Tensor>> qkv_s = c10::nullopt,
               c10::optional<std::vector<at::Tensor>> o_s = c10::nullopt,
               c10::optional<std::vector<at::Tensor>> gate_up_s = c10::nullopt,
-              c10::optional<std::vector<at::Tensor>> down_s = c10::nullopt)
+              c10::optional<std::vector<at::Tensor>> down_s = c10::nullopt, bool activations_fp8 = false)
       : embed_(embed), qkv_w_(qkv_w), o_w_(o_w), gate_up_w_(gate_up_w), down_w_(down_w), in_norm_(in_norm),
         post_norm_(post_norm), final_norm_(final_norm), lm_head_(lm_head), kc_(k_caches), vc_(v_caches),
         cos_sin_(cos_sin), hq_(hq), hkv_(hkv), d_(head_dim), eps_(eps), scale_(scale), vocab_(vocab_size),
@@ -177,11 +177,16 @@ class LlamaRunner {
                         "LlamaRunner: the scale of layers.", l, ".", names[k], " must be a contiguous float32 [",
                         w.size(0), "] on the device of the weight");
             wsz = std::max(wsz, w8_gemm_workspace(int64_t(1) << 20, w.size(0), w.size(1)));
+            // fp8 activations: the W8A8 GEMM's split-K partials share the buffer
+            if (activations_fp8 && w8a8_supported(w))
+              wsz = std::max(wsz, w8a8_gemm_workspace(int64_t(1) << 20, w.size(0), w.size(1)));
           }
         }
+        a8_ = activations_fp8;
         // split-K partials of w8_gemm, sized once for every row count so graph captures never allocate
         w8_ws_ = at::empty({std::max<int64_t>(wsz / 4, 4)}, embed_.options().dtype(at::kFloat));
       } else {
+        TORCH_CHECK(!activations_fp8, "LlamaRunner: fp8 activations need fp8 weights (the four weight scale lists)");
         for (int k = 0; k < 4; ++k)
           for (size_t l = 0; l < L; ++l)
             TORCH_CHECK((*wl[k])[l].scalar_type() != at::kFloat8_e4m3fn, "LlamaRunner: layers.", l, ".", names[k],
@@ -345,11 +350,33 @@ class LlamaRunner {
   }
 
   // bf16((x . code^T) * s) for any row count: w8_gemv at T <= 4 where its shape rule holds,
-  // else w8_gemm (gemm_w8.hip)
+  // else w8_gemm (gemm_w8.hip).  With fp8 activations (a8_) and T > 4: quantise the rows of x,
+  // then the FP8-MFMA GEMM (gemm_w8a8.hip); a weight outside its shape rule stays on
+  // linear_w8.  T <= 4 keeps the W8A16 GEMV: it streams each weight byte once and is
+  // bandwidth-bound there, so FP8 activations would add a quantiser launch and buy nothing.
+  bool a8_route(int64_t T, const at::Tensor& w) const { return a8_ && T > 4 && w8a8_supported(w); }
   at::Tensor proj_w8(const at::Tensor& x, const at::Tensor& w, const at::Tensor& s) {
     at::Tensor out = at::empty({x.size(0), w.size(0)}, x.options());
-    linear_w8(out, x, w, s, w8_ws_, 0);
+    if (a8_route(x.size(0), w)) linear_w8a8(out, x, w, s, w8_ws_, 0);
+    else linear_w8(out, x, w, s, w8_ws_, 0);
     return out;
+  }
+  // down projection of the SwiGLU: bf16(silu(g) * u) of gu [T, 2F] times w.  With fp8
+  // activations the quantiser forms the product itself (silu_mul mode) and the [T, F] bf16
+  // intermediate never goes to memory.
+  at::Tensor proj_w8_silu(const at::Tensor& gu, const at::Tensor& w, const at::Tensor& s) {
+    const int64_t T = gu.size(0), F = gu.size(1) / 2;
+    if (a8_route(T, w)) {
+      at::Tensor out = at::empty({T, w.size(0)}, gu.options());
+      at::Tensor xq = at::empty({T, F}, gu.options().dtype(at::kFloat8_e4m3fn));
+      at::Tensor xs = at::empty({T}, gu.options().dtype(at::kFloat));
+      quantize_rows_fp8(xq, xs, gu, true);
+      w8a8_gemm(out, xq, xs, w, s, w8_ws_, 0);
+      return out;
+    }
+    at::Tensor a = at::empty({T, F}, gu.options());
+    silu_and_mul(a, gu);
+    return proj_w8(a, w, s);
   }
 
   // silu(x . w[:F]^T) * (x . w[F:]^T) for any row count (same routing as proj)
@@ -476,9 +503,7 @@ class LlamaRunner {
       all_reduce(o);
       fused_add_rmsnorm(o, residual, post_norm_[l], eps_);
       at::Tensor gu = proj_w8(o, gate_up_w_[l], gate_up_s_[l]);
-      at::Tensor a = at::empty({T, gate_up_w_[l].size(0) / 2}, o.options());
-      silu_and_mul(a, gu);
-      at::Tensor dn = proj_w8(a, down_w_[l], down_s_[l]);
+      at::Tensor dn = proj_w8_silu(gu, down_w_[l], down_s_[l]);
       all_reduce(dn);
       fused_add_rmsnorm(dn, residual, l + 1 < L ? in_norm_[l + 1] : final_norm_, eps_);
       x = dn;
@@ -821,7 +846,8 @@ class LlamaRunner {
   bool qknorm_ = false;
   std::vector<at::Tensor> qkv_s_, o_s_, gate_up_s_, down_s_;   // per-layer f32 row scales of fp8 weights, empty without
   bool w8_ = false;            // the four projections of every layer are float8_e4m3fn codes + scales
-  at::Tensor w8_ws_;           // split-K workspace of w8_gemm
+  at::Tensor w8_ws_;           // split-K workspace of w8_gemm / w8a8_gemm
+  bool a8_ = false;            // fp8 activations: T > 4 projections on the W8A8 kernels (gemm_w8a8.hip)
   c10::optional<at::Tensor> q_norm(int64_t l) const {
     return qknorm_ ? c10::optional<at::Tensor>(q_norm_[l]) : c10::nullopt;
   }
@@ -1453,7 +1479,7 @@ void bind_runners(py::module_& m) {
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<int64_t>>,
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
-                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>>(),
+                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>, bool>(),
            py::arg("embed"), py::arg("qkv_w"), py::arg("o_w"), py::arg("gate_up_w"), py::arg("down_w"),
            py::arg("in_norm"), py::arg("post_norm"), py::arg("final_norm"), py::arg("lm_head"), py::arg("k_caches"),
            py::arg("v_caches"), py::arg("cos_sin"), py::arg("hq"), py::arg("hkv"), py::arg("head_dim"),
@@ -1461,7 +1487,8 @@ void bind_runners(py::module_& m) {
            py::arg("process_group"), py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0,
            py::arg("qkv_b") = py::none(), py::arg("windows") = py::none(),
            py::arg("q_norm") = py::none(), py::arg("k_norm") = py::none(), py::arg("qkv_s") = py::none(),
-           py::arg("o_s") = py::none(), py::arg("gate_up_s") = py::none(), py::arg("down_s") = py::none())
+           py::arg("o_s") = py::none(), py::arg("gate_up_s") = py::none(), py::arg("down_s") = py::none(),
+           py::arg("activations_fp8") = false)
       .def("forward", &LlamaRunner::forward, py::call_guard<py::gil_scoped_release>());
   py::class_<BertRunner>(m, "BertRunner")
       .def(py::init<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<std::vector<at::Tensor>>,

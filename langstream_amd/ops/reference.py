@@ -64,6 +64,39 @@ def linear_w8(x, codes, s, dtype=None):
     return y
 
 
+# ---- fp8 activations (opt-in, W8A8).  Each row of a projection's input is quantised on the
+# fly: xs[m] = max_k |x[m, k]| / 448 in f32 (1 for a zero row), inv = 1.0f / xs[m],
+# code = e4m3fn(RNE(clamp(f32(x) * inv, -448, 448))); then
+#   y[m, n] = bf16((sum_k code_x[m, k] * code_w[n, k]) * xs[m] * ws[n]).
+def quantize_rows_fp8(x, silu_mul: bool = False):
+    """(xq, xs) of x [M, K]; with ``silu_mul`` x is gu [M, 2F] and the rows quantised are
+    silu_and_mul(gu), rounded to x's dtype first as the kernel of that name does."""
+    if silu_mul:
+        x = silu_and_mul(x)
+    xf = x.float()
+    amax = xf.abs().amax(dim=1)
+    xs = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax)).to(torch.float32)
+    inv = 1.0 / xs
+    xq = (xf * inv[:, None]).clamp(-FP8_MAX, FP8_MAX).to(FP8_DTYPE)
+    return xq.contiguous(), xs.contiguous()
+
+
+def w8a8_gemm(xq, xs, codes, ws, dtype=None, out_dtype=torch.bfloat16):
+    """(code_x . code_w^T) * xs[:, None] * ws accumulated in f32 (or `dtype`); returns
+    `out_dtype` with the default f32 compute, else the compute dtype."""
+    ct = dtype or torch.float32
+    y = (xq.to(ct) @ codes.to(ct).t()) * xs.to(ct)[:, None] * ws.to(ct)
+    return y.to(out_dtype) if dtype is None else y
+
+
+def linear_w8a8(x, codes, ws, dtype=None, silu_mul: bool = False):
+    """The W8A8 projection on the CPU: quantize_rows_fp8, then w8a8_gemm (``dtype``: the
+    accumulation type, float64 for an oracle; the quantisation is f32 either way)."""
+    xq, xs = quantize_rows_fp8(x, silu_mul)
+    return w8a8_gemm(xq, xs, codes, ws, dtype,
+                     x.dtype if x.dtype in (torch.bfloat16, torch.float16) else torch.float32)
+
+
 def rmsnorm(x, w, eps):
     xf = x.float()
     return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * w.float()).to(x.dtype)

@@ -22,6 +22,9 @@ Configuration (``local-gpu-configuration`` resource):
   auto: what the checkpoint holds, bf16 for presets; fp8 on a bf16 checkpoint or preset quantises
   the four projections of every layer at load, e4m3 codes with one scale per output row; bf16 on an
   fp8 checkpoint is refused),
+  activations-dtype (bf16 | fp8; unset: the LS_ACTIVATIONS_DTYPE environment variable, else bf16.
+  fp8 needs fp8 weights: steps of more than 4 rows quantise each projection's input rows to e4m3
+  with one dynamic scale per row and run on the FP8 matrix instructions; never set by a checkpoint),
   sliding-window (true | false; unset: the LS_SLIDING_WINDOW environment variable, else false.
   A model-path with an active sliding window, Mistral or Qwen2 with use_sliding_window: true
   serves every position with windowed attention in the layers that have a window, false only
@@ -179,7 +182,10 @@ class ServiceRegistry:
                     sd = shard_llama(sd, mcfg, self.tp.rank, self.tp.world)
             elif wd == "auto":
                 wd = "bf16"
-            model_ = LlamaModel(mcfg, device=device, dtype=dtype, tp=self.tp, weights_dtype=wd)
+            ad = str(c.get("activations-dtype") or os.environ.get("LS_ACTIVATIONS_DTYPE") or "bf16").lower()
+            if ad not in ("bf16", "fp8"):
+                raise ValueError(f"activations-dtype {ad!r}: expected bf16 or fp8")
+            model_ = LlamaModel(mcfg, device=device, dtype=dtype, tp=self.tp, weights_dtype=wd, activations_dtype=ad)
             if sd is not None:
                 model_.load_state_dict(sd)
                 del sd
