@@ -343,7 +343,10 @@ RESOURCE_MODELS: Dict[str, Model] = {
         "weights-dtype": S("Element type of the four projection weights of every layer: auto (what the checkpoint "
                            "holds; bf16 for presets), bf16 or fp8 (e4m3 codes with one scale per output row, "
                            "activations stay bf16; a bf16 checkpoint or preset is quantised at load; bf16 on an "
-                           "fp8 checkpoint is refused); unset: the LS_WEIGHTS_DTYPE environment variable, else auto."),
+                           "fp8 checkpoint is refused; an AWQ or GPTQ checkpoint holds int4 weights, 4-bit codes "
+                           "with a scale and a zero point per group of input columns, and is served as such under "
+                           "auto, bf16 and fp8 on it are refused); unset: the LS_WEIGHTS_DTYPE environment "
+                           "variable, else auto."),
         "activations-dtype": S("Element type of the projection inputs: bf16, or fp8 (needs fp8 weights; steps of "
                                "more than 4 rows quantise each projection's input rows to e4m3 with one dynamic "
                                "scale per row and run on the FP8 matrix instructions); unset: the "

@@ -193,18 +193,33 @@ def _a8(x: torch.Tensor, w: torch.Tensor, a8: bool) -> bool:
     return a8 and x.shape[0] > 4 and ops.w8a8_supported(w)
 
 
-def _linear(x: torch.Tensor, w: torch.Tensor, s: Optional[torch.Tensor] = None, a8: bool = False) -> torch.Tensor:
+def _linear(x: torch.Tensor, w: torch.Tensor, s: Optional[torch.Tensor] = None, a8: bool = False,
+            z: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x . w^T; with row scales ``s`` the weight is fp8 codes and the W8A16 projection runs
     (ops.linear_w8: the HIP kernels on the GPU, ops.reference.linear_w8 on the CPU), or with
-    ``a8`` the W8A8 one where _a8 allows it (ops.linear_w8a8)."""
+    ``a8`` the W8A8 one where _a8 allows it (ops.linear_w8a8).  With zero points ``z`` the weight
+    is packed int4 codes, ``s`` its group scales, and the W4A16 projection runs (ops.linear_w4)."""
+    if z is not None:
+        return ops.linear_w4(x, w, s, z)
     if s is not None:
         return ops.linear_w8a8(x, w, s) if _a8(x, w, a8) else ops.linear_w8(x, w, s)
     return ops.gemm_prefill(x, w) if _pgemm(x, w, False) else F.linear(x, w)
 
 
-WEIGHTS_DTYPES = ("bf16", "fp8")
+WEIGHTS_DTYPES = ("bf16", "fp8", "int4")
+INT4_GROUP = ref.INT4_GROUP   # input columns per scale / zero point when a wider weight is quantised here
 ACTIVATIONS_DTYPES = ("bf16", "fp8")
-W8_NAMES = ("qkv", "o", "gate_up", "down")   # the projections an fp8 model stores as codes + row scales
+W8_NAMES = ("qkv", "o", "gate_up", "down")   # the projections an fp8 / int4 model stores as codes + scales
+
+
+def int4_group(name: str, N: int, K: int, group: int = INT4_GROUP) -> int:
+    """The group size an [N, K] projection is quantised with (``group``, or K where K is not
+    larger); a shape the W4 kernels do not take is refused by ``name``, never rerouted."""
+    G = K if group <= 0 or group >= K else group
+    if N % 64 or K % 64 or K % G or G % 64:
+        raise ValueError(f"{name} {(N, K)}: int4 weights need both dimensions to be multiples of 64 and a group "
+                         f"size ({G}) that is a multiple of 64 and divides K")
+    return G
 
 
 def tp_kv_heads(num_kv_heads: int, world: int) -> int:
@@ -219,7 +234,8 @@ def tp_kv_heads(num_kv_heads: int, world: int) -> int:
 
 
 class LlamaLayer:
-    def __init__(self, cfg: LlamaConfig, tp: TPInfo, device, dtype, fp8: bool = False):
+    def __init__(self, cfg: LlamaConfig, tp: TPInfo, device, dtype, fp8: bool = False, int4: bool = False,
+                 name: str = "layers.?"):
         H, D = cfg.hidden_size, cfg.head_dim
         assert cfg.num_heads % tp.world == 0, "TP must divide the query heads"
         assert cfg.intermediate_size % tp.world == 0
@@ -240,6 +256,15 @@ class LlamaLayer:
                 codes, sc = ref.quantize_weight_fp8(getattr(self, n + "_w"))
                 setattr(self, n + "_w", codes)
                 setattr(self, n + "_s", sc)
+        # int4 weights: packed 4-bit codes [N, K / 2] + f32 scale and uint8 zero point per group of
+        # INT4_GROUP input columns ([N, K / G]; ops.reference.quantize_weight_int4), likewise
+        self.qkv_z = self.o_z = self.gate_up_z = self.down_z = None
+        if int4:
+            for n in W8_NAMES:
+                w = getattr(self, n + "_w")
+                G = int4_group(f"{name}.{n}_w", w.shape[0], w.shape[1])
+                for suffix, t in zip(("_w", "_s", "_z"), ref.quantize_weight_int4(w, G)):
+                    setattr(self, n + suffix, t)
         self.in_norm = torch.ones(H, device=device, dtype=dtype)
         self.post_norm = torch.ones(H, device=device, dtype=dtype)
         # packed like the rows of qkv_w: q heads, k heads, v heads
@@ -253,6 +278,8 @@ class LlamaLayer:
         t = [self.qkv_w, self.o_w, self.gate_up_w, self.down_w, self.in_norm, self.post_norm]
         if self.qkv_s is not None:
             t += [self.qkv_s, self.o_s, self.gate_up_s, self.down_s]
+        if self.qkv_z is not None:
+            t += [self.qkv_z, self.o_z, self.gate_up_z, self.down_z]
         if self.qkv_b is not None:
             t.append(self.qkv_b)
         if self.q_norm is not None:
@@ -276,7 +303,9 @@ class LlamaModel:
         # with one dynamic f32 scale per row and run the W8A8 kernels (ops/csrc/gemm_w8a8.hip)
         self.activations_dtype = activations_dtype
         # "fp8": the four projections of every layer are float8_e4m3fn codes with one f32 scale
-        # per output row (W8A16: activations, embed, lm_head and the norms keep `dtype`)
+        # per output row (W8A16: activations, embed, lm_head and the norms keep `dtype`).
+        # "int4": they are packed 4-bit codes with an f32 scale and a zero point per group of
+        # input columns (W4A16, ops/csrc/gemm_w4.hip; the AWQ / GPTQ family)
         self.weights_dtype = weights_dtype
         self.cfg = cfg
         self.device = torch.device(device)
@@ -290,8 +319,9 @@ class LlamaModel:
             self.vocab_per_rank = (cfg.vocab_size + self.tp.world - 1) // self.tp.world
             self.vocab_start = self.tp.rank * self.vocab_per_rank
             self.embed = (torch.randn(self.vocab_per_rank, H, device=self.device) * 0.02).to(dtype)
-            self.layers = [LlamaLayer(cfg, self.tp, self.device, dtype, fp8=weights_dtype == "fp8")
-                           for _ in range(cfg.num_layers)]
+            self.layers = [LlamaLayer(cfg, self.tp, self.device, dtype, fp8=weights_dtype == "fp8",
+                                      int4=weights_dtype == "int4", name=f"layers.{i}")
+                           for i in range(cfg.num_layers)]
             self.final_norm = torch.ones(H, device=self.device, dtype=dtype)
             self.lm_head = self.embed if cfg.tie_embeddings else (
                 torch.randn(self.vocab_per_rank, H, device=self.device) * 0.02).to(dtype)
@@ -327,8 +357,10 @@ class LlamaModel:
             names += ("qkv_b",)
         if self.cfg.qk_norm:
             names += ("q_norm", "k_norm")
-        if self.weights_dtype == "fp8":
+        if self.weights_dtype in ("fp8", "int4"):
             names += tuple(n + "_s" for n in W8_NAMES)
+        if self.weights_dtype == "int4":
+            names += tuple(n + "_z" for n in W8_NAMES)
         return names
 
     def state_dict(self) -> dict:
@@ -345,14 +377,21 @@ class LlamaModel:
         self.final_norm.copy_(sd["final_norm"])
         if not self.cfg.tie_embeddings:
             self.lm_head.copy_(sd["lm_head"])
-        fp8 = self.weights_dtype == "fp8"
+        fp8, int4 = self.weights_dtype == "fp8", self.weights_dtype == "int4"
         for i, l in enumerate(self.layers):
             for n in self._layer_names():
                 key = f"layers.{i}.{n}"
-                if fp8 and n.endswith("_s"):
+                if (fp8 or int4) and n.endswith(("_s", "_z")):
                     continue   # loaded with its weight below
                 src = sd[key]
                 if n.endswith("_w") and n[:-2] in W8_NAMES:
+                    zkey = f"layers.{i}.{n[:-2]}_z"
+                    if not int4 and zkey in sd:
+                        raise ValueError(f"{key} holds int4 codes ({zkey} is present) but the model's weights_dtype "
+                                         f"is {self.weights_dtype!r}; build the model with weights_dtype='int4'")
+                    if int4:
+                        self._load_int4(l, n[:-2], key, sd)
+                        continue
                     if not fp8 and ref.is_fp8(src):
                         raise ValueError(f"{key} holds float8_e4m3fn codes but the model's weights_dtype is "
                                          f"'bf16'; build the model with weights_dtype='fp8'")
@@ -373,6 +412,32 @@ class LlamaModel:
                         getattr(l, n[:-2] + "_s").copy_(sc)
                         continue
                 getattr(l, n).copy_(src)
+
+    def _load_int4(self, layer: LlamaLayer, n: str, key: str, sd: dict) -> None:
+        """One projection of an int4 model: the (codes, scale, zero) triple of the state dict
+        as it is (its group size may differ from the one the model was built with), or a wider
+        weight quantised here with the one rule."""
+        src = sd[key]
+        skey, zkey = key[:-2] + "_s", key[:-2] + "_z"
+        N, K = getattr(layer, n + "_w").shape[0], 2 * getattr(layer, n + "_w").shape[1]
+        if src.dtype == torch.uint8:
+            if skey not in sd or zkey not in sd:
+                raise ValueError(f"{key} holds int4 codes but {skey} or {zkey} is missing")
+            if ref.is_fp8(src) or tuple(src.shape) != (N, K // 2):
+                raise ValueError(f"{key} has shape {tuple(src.shape)}, expected packed codes {(N, K // 2)}")
+            sc, zp = sd[skey].to(torch.float32), sd[zkey]
+            if sc.dim() != 2 or sc.shape[0] != N or zp.shape != sc.shape or zp.dtype != torch.uint8:
+                raise ValueError(f"{skey} / {zkey} must be f32 and uint8 [N = {N}, K / G], got "
+                                 f"{tuple(sc.shape)} and {tuple(zp.shape)} {zp.dtype}")
+            int4_group(key, N, K, K // sc.shape[1] if sc.shape[1] and K % sc.shape[1] == 0 else 1)
+            t = (src, sc, zp)
+        elif ref.is_fp8(src):
+            raise ValueError(f"{key} holds float8_e4m3fn codes but the model's weights_dtype is 'int4'")
+        else:
+            t = ref.quantize_weight_int4(src.to(self.device), int4_group(key, N, K))
+        for suffix, v in zip(("_w", "_s", "_z"), t):
+            setattr(layer, n + suffix, v.to(self.device).contiguous())
+        self._runner = None
 
     # ------------------------------------------------------------------ forward
     def embed_tokens(self, ids: torch.Tensor) -> torch.Tensor:
@@ -396,7 +461,7 @@ class LlamaModel:
         a8 = self.activations_dtype == "fp8"
         for li, layer in enumerate(self.layers):
             kc, vc = kv_caches[li]
-            qkv = _linear(x, layer.qkv_w, layer.qkv_s, a8)
+            qkv = _linear(x, layer.qkv_w, layer.qkv_s, a8, layer.qkv_z)
             ops.rope_and_cache(qkv, meta.positions, self.cos_sin, meta.slots, kc, vc, self.hq, self.hkv,
                                k_scale=ks, v_scale=vs, bias=layer.qkv_b, q_norm=layer.q_norm, k_norm=layer.k_norm,
                                norm_eps=eps)
@@ -417,11 +482,11 @@ class LlamaModel:
                 ops.paged_prefill_attention(q, kc, vc, meta.p_block_tables, meta.q_start, meta.q_len, meta.ctx_len,
                                             meta.tiles, self.hq, self.scale, out=attn, k_scale=ks, v_scale=vs,
                                             window=win)
-            o = _linear(attn, layer.o_w, layer.o_s, a8)
+            o = _linear(attn, layer.o_w, layer.o_s, a8, layer.o_z)
             self.tp.all_reduce(o)
             ops.fused_add_rmsnorm(o, residual, layer.post_norm, eps)
             if layer.gate_up_s is not None:
-                gu = _linear(o, layer.gate_up_w, layer.gate_up_s, a8)
+                gu = _linear(o, layer.gate_up_w, layer.gate_up_s, a8, layer.gate_up_z)
                 if _a8(gu, layer.down_w, a8):
                     # the quantiser forms bf16(silu(g) * u) itself: no [T, F] intermediate
                     d = ops.linear_w8a8(gu, layer.down_w, layer.down_s, silu_mul=True)
@@ -433,7 +498,7 @@ class LlamaModel:
             else:
                 a = ops.silu_and_mul(F.linear(o, layer.gate_up_w))
             if a is not None:
-                d = _linear(a, layer.down_w, layer.down_s, a8)
+                d = _linear(a, layer.down_w, layer.down_s, a8, layer.down_z)
             self.tp.all_reduce(d)
             nxt = self.layers[li + 1].in_norm if li + 1 < len(self.layers) else self.final_norm
             ops.fused_add_rmsnorm(d, residual, nxt, eps)
@@ -461,8 +526,9 @@ class LlamaModel:
             [self.cfg.layer_window(i) for i in range(len(L))],
             [l.q_norm for l in L] if self.cfg.qk_norm else None,
             [l.k_norm for l in L] if self.cfg.qk_norm else None,
-            *([[getattr(l, n + "_s") for l in L] for n in W8_NAMES] if self.weights_dtype == "fp8" else []),
-            activations_fp8=self.activations_dtype == "fp8")
+            *([[getattr(l, n + "_s") for l in L] for n in W8_NAMES] if self.weights_dtype in ("fp8", "int4") else []),
+            activations_fp8=self.activations_dtype == "fp8",
+            **({n + "_z": [getattr(l, n + "_z") for l in L] for n in W8_NAMES} if self.weights_dtype == "int4" else {}))
         self._runner = (key, runner, kv_caches)
         return runner
 

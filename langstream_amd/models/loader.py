@@ -57,7 +57,7 @@ def load_packed(path: str, device="cpu") -> Dict[str, torch.Tensor]:
     sd = dict(iter_checkpoint(path))
     if any(k.startswith("model.layers.") or k == "model.embed_tokens.weight" for k in sd):
         cfg = llama_config_from_hf(path) if os.path.isdir(path) else None
-        sd = convert_hf_llama(sd, cfg)
+        sd = convert_hf_llama(sd, cfg, hf_quantization_config(path) if os.path.isdir(path) else None)
     elif any(k.startswith(("bert.", "encoder.layer.", "embeddings.")) for k in sd):
         sd = convert_hf_bert(sd)
     return {k: v.to(device) for k, v in sd.items()}
@@ -73,6 +73,13 @@ def hf_model_type(model_dir: str) -> str:
     """``model_type`` of a Hugging Face directory's ``config.json`` ("llama" when absent)."""
     with open(os.path.join(model_dir, "config.json")) as f:
         return json.load(f).get("model_type", "llama")
+
+
+def hf_quantization_config(model_dir: str) -> Optional[dict]:
+    """``quantization_config`` of a Hugging Face directory's ``config.json`` (None when absent)."""
+    with open(os.path.join(model_dir, "config.json")) as f:
+        q = json.load(f).get("quantization_config")
+    return q if isinstance(q, dict) else None
 
 
 def _checkpoint_names(model_dir: str) -> set:
@@ -224,14 +231,107 @@ def llama_config_from_hf(model_dir: str, sliding_window: bool = False) -> LlamaC
         window_layers=win_layers)
 
 
-def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = None) -> Dict[str, torch.Tensor]:
+AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)   # nibble i of an AWQ word holds column 8 * col + AWQ_ORDER[i]
+
+
+def _unpack_nibbles(t: torch.Tensor, order=None) -> torch.Tensor:
+    """int32 [R, C] -> uint8 [R, 8 C]: nibble i (lowest first) of word c is column 8 c + i, or
+    with ``order`` column 8 c + order[i]."""
+    nib = ((t.to(torch.int32).unsqueeze(-1) >> (4 * torch.arange(8, dtype=torch.int32))) & 15).to(torch.uint8)
+    if order is not None:
+        placed = torch.empty_like(nib)
+        placed[..., list(order)] = nib
+        nib = placed
+    return nib.reshape(t.shape[0], 8 * t.shape[1])
+
+
+def _int4_scheme(q: Optional[dict]) -> Tuple[str, int, int]:
+    """(method, group_size, zero offset) of the ``quantization_config`` of a checkpoint with
+    ``qweight`` tensors: GPTQ (4 bits, no ``desc_act``; ``checkpoint_format`` "gptq" stores
+    zero - 1, "gptq_v2" the zero point) or AWQ (4 bits, version "gemm", with zero points).
+    Everything else is refused by the name of the field."""
+    if not isinstance(q, dict):
+        raise ValueError("the checkpoint holds qweight tensors but config.json has no quantization_config "
+                         "(gptq or awq expected)")
+    method = str(q.get("quant_method", "")).lower()
+    if method not in ("gptq", "awq"):
+        raise ValueError(f"quantization_config.quant_method = {q.get('quant_method')!r}: qweight tensors are "
+                         f"supported for gptq and awq only")
+    if q.get("bits") != 4:
+        raise ValueError(f"quantization_config.bits = {q.get('bits')!r}: only 4-bit {method} weights are supported")
+    off = 0
+    if method == "gptq":
+        if q.get("desc_act", False):
+            raise ValueError("quantization_config.desc_act = true: activation-ordered GPTQ groups are not "
+                             "supported (g_idx must be k // group_size)")
+        fmt = q.get("checkpoint_format") or "gptq"
+        if fmt not in ("gptq", "gptq_v2"):
+            raise ValueError(f"quantization_config.checkpoint_format = {fmt!r}: expected gptq or gptq_v2")
+        off = 1 if fmt == "gptq" else 0
+    else:
+        if str(q.get("version", "gemm")).lower() != "gemm":
+            raise ValueError(f"quantization_config.version = {q.get('version')!r}: only the AWQ gemm layout is "
+                             f"supported")
+        if not q.get("zero_point", True):
+            raise ValueError("quantization_config.zero_point = false: symmetric AWQ checkpoints are not supported")
+    return method, int(q.get("group_size", 128)), off
+
+
+def _int4_proj(hf, take, name: str, scheme) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """One AWQ / GPTQ ``..._proj`` -> (codes uint8 [N, K / 2], scale f32 [N, K / G], zero uint8
+    [N, K / G]) in the layout of ops.reference.pack_weight_int4."""
+    from ..ops import reference as ref
+    method, gs, off = scheme
+    for part in ("qzeros", "scales"):
+        if f"{name}.{part}" not in hf:
+            raise ValueError(f"checkpoint tensor {name + '.qweight'!r} comes without {name + '.' + part!r}")
+    qw, qz, sc = take(name + ".qweight"), take(name + ".qzeros"), take(name + ".scales")
+    if qw.dtype != torch.int32 or qz.dtype != torch.int32 or qw.dim() != 2 or qz.dim() != 2 or sc.dim() != 2:
+        raise ValueError(f"checkpoint tensors {name}.qweight / .qzeros must be 2-D int32 and .scales 2-D")
+    if method == "gptq":
+        q = _unpack_nibbles(qw.t().contiguous())                     # [K / 8, N] -> [N, K]
+        zero = _unpack_nibbles(qz).to(torch.int32) + off             # [K / G, N]
+    else:
+        q = _unpack_nibbles(qw, AWQ_ORDER).t().contiguous()          # [K, N / 8] -> [N, K]
+        zero = _unpack_nibbles(qz, AWQ_ORDER).to(torch.int32)
+    N, K = q.shape
+    G = K if gs == -1 else gs
+    if G <= 0 or G % 64 or K % G:
+        raise ValueError(f"quantization_config.group_size = {gs} for {name} with K = {K}: the group size must be "
+                         f"a multiple of 64 that divides K (or -1: one group per row)")
+    if tuple(sc.shape) != (K // G, N) or tuple(zero.shape) != (K // G, N):
+        raise ValueError(f"checkpoint tensors {name}.scales {tuple(sc.shape)} / .qzeros do not have K / G = "
+                         f"{K // G} rows and N = {N} columns")
+    if int(zero.max()) > 15:
+        raise ValueError(f"checkpoint tensor {name + '.qzeros'!r} holds a zero point of 16 (stored 15 in the "
+                         f"gptq format): outside 0..15, not supported")
+    if name + ".g_idx" in hf:
+        if not torch.equal(take(name + ".g_idx").to(torch.int64), torch.arange(K) // G):
+            raise ValueError(f"checkpoint tensor {name + '.g_idx'!r} is not k // group_size: activation-ordered "
+                             f"groups are not supported")
+    scale = sc.t().to(torch.float32).contiguous()
+    if not bool((scale > 0).all()) or not bool(torch.isfinite(scale).all()):
+        raise ValueError(f"checkpoint tensor {name + '.scales'!r} must be positive and finite")
+    return ref.pack_weight_int4(q), scale, zero.t().to(torch.uint8).contiguous()
+
+
+def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = None,
+                     quantization: Optional[dict] = None) -> Dict[str, torch.Tensor]:
     """HF ``LlamaForCausalLM`` / ``MistralForCausalLM`` / ``Qwen2ForCausalLM`` /
     ``Qwen3ForCausalLM`` names -> packed names (fused qkv / gate_up, ``q/k/v_proj.bias`` fused
     into ``qkv_b``, ``self_attn.q_norm.weight`` / ``k_norm.weight`` as ``q_norm`` / ``k_norm``,
     both or neither).  A checkpoint is loaded whole or refused: a tensor that is not consumed
     (``o_proj.bias``, ``mlp.*.bias``, ...) raises ValueError naming it; ``rotary_emb.inv_freq``
-    is the only name skipped."""
+    is the only name skipped.
+
+    AWQ and GPTQ checkpoints (``..._proj.qweight`` / ``.qzeros`` / ``.scales``; ``quantization``
+    is the ``quantization_config`` of their ``config.json``, see ``_int4_scheme``) become int4
+    triples ``{key}_w`` / ``_s`` / ``_z`` in the layout of ``ops.reference.pack_weight_int4``."""
     used = set()
+    scheme = _int4_scheme(quantization) if any(n.endswith(".qweight") for n in hf) else None
+    if "lm_head.qweight" in hf:
+        raise ValueError("checkpoint tensor 'lm_head.qweight': a quantised lm_head is not supported; only the "
+                         "layer projections may be int4")
     kinds = set()        # {"fp8", "wide"} over every projection: one kind per checkpoint
     dropped = []         # activation-scale tensors consumed and not used
 
@@ -242,6 +342,9 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = N
     def proj(name):
         """(weight, f32 [N] scale or None) of one ``..._proj``: a float8_e4m3fn weight comes with a
         sibling ``weight_scale`` (scalar, [1], [N] or [N, 1]; per-tensor scales are broadcast)."""
+        if name + ".qweight" in hf:
+            kinds.add("int4")
+            return _int4_proj(hf, take, name, scheme)
         w = take(name + ".weight")
         for extra in ("input_scale", "input_scale_ub"):
             if name + "." + extra in hf:
@@ -249,7 +352,7 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = N
                 used.add(name + "." + extra)
         if w.dtype != FP8:
             kinds.add("wide")
-            return w, None
+            return w, None, None
         kinds.add("fp8")
         sn = name + ".weight_scale"
         if sn not in hf:
@@ -262,10 +365,15 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = N
                              f"(per-tensor or per-channel scales only)")
         if not bool((sc > 0).all()) or not bool(torch.isfinite(sc).all()):
             raise ValueError(f"checkpoint tensor {sn!r} must be positive and finite")
-        return w, sc.contiguous()
+        return w, sc.contiguous(), None
 
     def fuse(key, names):
-        ws, ss = zip(*[proj(n) for n in names])
+        ws, ss, zs = zip(*[proj(n) for n in names])
+        if any(x is None for x in zs) != all(x is None for x in zs):
+            raise ValueError(f"checkpoint mixes int4 and wider projections in {key} ({', '.join(names)})")
+        if zs[0] is not None:
+            out[f"{key}_w"], out[f"{key}_s"], out[f"{key}_z"] = (torch.cat(t, 0) for t in (ws, ss, zs))
+            return
         if any(x is None for x in ss) != all(x is None for x in ss):
             raise ValueError(f"checkpoint mixes fp8 and wider projections in {key} ({', '.join(names)})")
         out[f"{key}_w"] = ws[0] if len(ws) == 1 else _cat_rows(ws)
@@ -278,7 +386,7 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = N
         if out[n].dtype == FP8:
             raise ValueError(f"checkpoint tensor for {n} is float8_e4m3fn: only the layer projections may be fp8")
     i = 0
-    while f"model.layers.{i}.self_attn.q_proj.weight" in hf:
+    while any(f"model.layers.{i}.self_attn.q_proj.{w}" in hf for w in ("weight", "qweight")):
         p = f"model.layers.{i}."
         qkv = [p + f"self_attn.{n}_proj" for n in "qkv"]
         fuse(f"layers.{i}.qkv", qkv)
@@ -299,6 +407,9 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = N
         i += 1
     if cfg is not None:
         assert i == cfg.num_layers, f"checkpoint has {i} layers, config {cfg.num_layers}"
+    if "int4" in kinds and len(kinds) > 1:
+        raise ValueError("checkpoint mixes int4 (qweight) and other projection weights; the projections of a "
+                         "checkpoint are all int4, all fp8 or all bf16 / f16 / f32")
     if len(kinds) > 1:
         raise ValueError("checkpoint mixes fp8 (float8_e4m3fn) and wider projection weights; the projections "
                          "of a checkpoint are all fp8 or all bf16 / f16 / f32")
@@ -320,7 +431,10 @@ def _cat_rows(ts) -> torch.Tensor:
 
 
 def checkpoint_weights_dtype(sd: Dict[str, torch.Tensor]) -> str:
-    """"fp8" when the layer projections of a packed state dict are float8_e4m3fn codes, else "bf16"."""
+    """"fp8" when the layer projections of a packed state dict are float8_e4m3fn codes, "int4"
+    when they are packed 4-bit codes with zero points (``{name}_z``), else "bf16"."""
+    if any(k.endswith(tuple(f".{n}_z" for n in W8_NAMES)) for k in sd):
+        return "int4"
     keys = tuple(f".{n}_w" for n in W8_NAMES)
     return "fp8" if any(k.endswith(keys) and v.dtype == FP8 for k, v in sd.items()) else "bf16"
 
@@ -331,9 +445,26 @@ def shard_llama(sd: Dict[str, torch.Tensor], cfg: LlamaConfig, rank: int, world:
     (padded to a multiple of ``world``), replicated norms (the per-head ``q_norm`` / ``k_norm``
     included: every rank's heads share the one weight).  The row scales of fp8 weights follow
     the rows: ``qkv_s`` / ``gate_up_s`` are sliced like ``qkv_w`` / ``gate_up_w``; ``o_s`` /
-    ``down_s`` are replicated (those weights are cut along K, every rank keeps all rows)."""
+    ``down_s`` are replicated (those weights are cut along K, every rank keeps all rows).
+
+    int4 weights (``{name}_z`` present): the column shards cut codes, scales and zero points by
+    rows; the row shards ``o`` / ``down`` cut all three along K -- bytes of two codes, columns
+    of one group -- and are refused unless K / world is a multiple of the group size."""
     if world == 1:
         return dict(sd)
+
+    def k_cut(k, v, lo, hi):
+        """Columns [lo, hi) of K of an ``o`` / ``down`` tensor (int4: codes, scales or zero points)."""
+        base = k[:-2]
+        if base + "_z" not in sd:
+            return v[:, lo:hi] if k.endswith("_w") else v     # bf16 / fp8: the row scales are replicated
+        K, NG = 2 * sd[base + "_w"].shape[1], sd[base + "_s"].shape[1]
+        G = K // NG
+        if lo % G or hi % G:
+            raise ValueError(f"{base}_w: K / TP = {hi - lo} is not a multiple of the int4 group size {G}; this "
+                             f"TP degree cannot shard the checkpoint")
+        return v[:, lo // 2:hi // 2] if k.endswith("_w") else v[:, lo // G:hi // G]
+
     from .llama import tp_kv_heads
     D = cfg.head_dim
     hq, hkv, f = cfg.num_heads // world, tp_kv_heads(cfg.num_kv_heads, world), cfg.intermediate_size // world
@@ -343,17 +474,17 @@ def shard_llama(sd: Dict[str, torch.Tensor], cfg: LlamaConfig, rank: int, world:
     vpr = (cfg.vocab_size + world - 1) // world
     out = {}
     for k, v in sd.items():
-        if k.endswith((".qkv_w", ".qkv_b", ".qkv_s")):   # bias and scales are sliced like the rows they belong to
+        if k.endswith((".qkv_w", ".qkv_b", ".qkv_s", ".qkv_z")):   # bias and scales are sliced like the rows they belong to
             q, kk, vv = v[:Hq], v[Hq: Hq + Hkv], v[Hq + Hkv:]
             out[k] = _cat_rows([q[rank * hq * D:(rank + 1) * hq * D], kk[kv0 * D:(kv0 + hkv) * D],
                                 vv[kv0 * D:(kv0 + hkv) * D]])
-        elif k.endswith(".o_w"):
-            out[k] = v[:, rank * hq * D:(rank + 1) * hq * D]
-        elif k.endswith((".gate_up_w", ".gate_up_s")):
+        elif k.endswith((".o_w", ".o_s", ".o_z")):
+            out[k] = k_cut(k, v, rank * hq * D, (rank + 1) * hq * D)
+        elif k.endswith((".gate_up_w", ".gate_up_s", ".gate_up_z")):
             g, u = v[:F], v[F:]
             out[k] = _cat_rows([g[rank * f:(rank + 1) * f], u[rank * f:(rank + 1) * f]])
-        elif k.endswith(".down_w"):
-            out[k] = v[:, rank * f:(rank + 1) * f]
+        elif k.endswith((".down_w", ".down_s", ".down_z")):
+            out[k] = k_cut(k, v, rank * f, (rank + 1) * f)
         elif k in ("embed", "lm_head"):
             part = v[rank * vpr:(rank + 1) * vpr]
             if part.shape[0] < vpr:

@@ -217,10 +217,39 @@ def linear_w8(x, w, s, out=None, splits: int = 0):
     return r
 
 
+def linear_w4(x, w, s, z, out=None, splits: int = 0):
+    """W4A16 projection (ops/csrc/gemm_w4.hip): bf16(sum_g s[n, g] * sum_{k in g} x[m, k] *
+    (q[n, k] - z[n, g])) for bf16 x [M, K], packed 4-bit codes w uint8 [N, K / 2] (the layout
+    of ops.reference.pack_weight_int4), f32 scales s and uint8 zero points z [N, K / G].
+    M <= 4 runs on w4_gemv where its shape rule holds (K % 1024 == 0), everything else on
+    w4_gemm; ``splits`` > 0 forces the tiled kernel with that many K slices.  N % 64 == 0,
+    K % 64 == 0 and G % 64 == 0; anything else raises."""
+    if _gpu(x, w, s, z):
+        h = hip()
+        M, N, K = x.shape[0], w.shape[0], 2 * w.shape[1]
+        out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+        need = splits * M * N * 4 if splits > 0 else (h.w4_gemm_workspace(M, N, K) if N >= 64 and K >= 64 else 0)
+        h.linear_w4(out, x, w, s, z, _w8_workspace(x.device, need), splits)
+        return out
+    r = ref.linear_w4(x, w, s, z)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
+def w4_supported(w) -> bool:
+    """The shape rule of the W4 kernels: contiguous uint8 [N, K / 2], N % 64 == 0, K % 64 == 0
+    (the same rule on the CPU, so a model is refused alike on both)."""
+    return (w.dim() == 2 and w.dtype == torch.uint8 and w.is_contiguous() and w.shape[0] >= 64
+            and w.shape[0] % 64 == 0 and w.shape[1] >= 32 and w.shape[1] % 32 == 0)
+
+
 def w8_launch_counts(reset: bool = False) -> dict:
     """Launches of the W8 kernels per variant since the last reset: {"gemv": n,
-    "gemm_bm64_s4": n, ...} (tile rows and K slices of w8_gemm), and of the W8A8 kernels:
-    "a8_bm128_s2" (tile rows and K slices of w8a8_gemm), "quant", "quant_silu"."""
+    "gemm_bm64_s4": n, ...} (tile rows and K slices of w8_gemm), of the W8A8 kernels:
+    "a8_bm128_s2" (tile rows and K slices of w8a8_gemm), "quant", "quant_silu", and of the W4
+    kernels: "w4_gemv", "w4_bm64_s4" (tile rows and K slices of w4_gemm)."""
     return dict(hip().w8_launch_counts(reset))
 
 

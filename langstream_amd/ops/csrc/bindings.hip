@@ -105,5 +105,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("workspace"), py::arg("splits") = 0);
   m.def("linear_w8a8", &linear_w8a8, py::arg("out"), py::arg("x"), py::arg("w"), py::arg("ws"), py::arg("workspace"),
         py::arg("splits") = 0);
+  m.def("w4_supported", &w4_supported);
+  m.def("w4_gemv_supported", &w4_gemv_supported);
+  m.def("w4_gemm_workspace", &w4_gemm_workspace);
+  m.def("w4_gemm", &w4_gemm, py::arg("out"), py::arg("x"), py::arg("w"), py::arg("s"), py::arg("z"),
+        py::arg("workspace"), py::arg("splits") = 0);
+  m.def("w4_gemv", &w4_gemv);
+  m.def("linear_w4", &linear_w4, py::arg("out"), py::arg("x"), py::arg("w"), py::arg("s"), py::arg("z"),
+        py::arg("workspace"), py::arg("splits") = 0);
   bind_runners(m);
 }

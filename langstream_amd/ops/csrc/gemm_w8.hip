@@ -331,6 +331,8 @@ void gemv_launch_k(hipStream_t st, const at::Tensor& x, const at::Tensor& w, con
 
 }  // namespace
 
+int w8_pick_split(int64_t M, int64_t N, int64_t K) { return pick_split(M, N, K); }
+
 // The shape rule of the W8 kernels: fp8 codes, contiguous [N, K], N % 64 == 0, K % 64 == 0.
 bool w8_supported(const at::Tensor& w) {
   return w.dim() == 2 && w.scalar_type() == at::kFloat8_e4m3fn && w.is_contiguous() && w.size(0) % BN == 0 &&
@@ -409,5 +411,6 @@ pybind11::dict w8_launch_counts(bool reset) {
       d[pybind11::str("gemm_bm" + std::to_string(b ? 128 : 64) + "_s" + std::to_string(s))] = n;
     }
   w8a8_launch_counts(d, reset);   // a8_bm{BM}_s{S}, quant, quant_silu (gemm_w8a8.hip)
+  w4_launch_counts(d, reset);     // w4_gemv, w4_bm{BM}_s{S} (gemm_w4.hip)
   return d;
 }

@@ -257,6 +257,7 @@ void w8_gemm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s, at::Tenso
 void w8_gemv(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s);
 void linear_w8(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s, at::Tensor workspace, int64_t splits_force);
 pybind11::dict w8_launch_counts(bool reset);
+int w8_pick_split(int64_t M, int64_t N, int64_t K);   // the K slices w8_gemm cuts (shared with gemm_w4.hip)
 
 // ---------------------------------------------------------------------- gemm_w8a8.hip
 // W8A8 projections: per-row dynamic e4m3fn activation codes times the W8 weights on the FP8 MFMA.
@@ -268,6 +269,18 @@ void w8a8_gemm(at::Tensor out, at::Tensor xq, at::Tensor xs, at::Tensor w, at::T
 void linear_w8a8(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor ws, at::Tensor workspace,
                  int64_t splits_force);
 void w8a8_launch_counts(pybind11::dict& d, bool reset);   // adds its keys to the census of w8_launch_counts
+
+// ------------------------------------------------------------------------ gemm_w4.hip
+// W4A16 projections: 4-bit codes [N, K / 2] (two per byte), f32 scale and uint8 zero point [N, K / G].
+bool w4_supported(const at::Tensor& w);
+bool w4_gemv_supported(const at::Tensor& w);
+int64_t w4_gemm_workspace(int64_t M, int64_t N, int64_t K);
+void w4_gemm(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s, at::Tensor z, at::Tensor workspace,
+             int64_t splits_force);
+void w4_gemv(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s, at::Tensor z);
+void linear_w4(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s, at::Tensor z, at::Tensor workspace,
+               int64_t splits_force);
+void w4_launch_counts(pybind11::dict& d, bool reset);   // adds its keys to the census of w8_launch_counts
 
 // -------------------------------------------------------------------------- runner.hip
 void bind_runners(pybind11::module_& m);

@@ -103,7 +103,11 @@ class LlamaRunner {
               c10::optional<std::vector<at::Tensor>> qkv_s = c10::nullopt,
               c10::optional<std::vector<at::Tensor>> o_s = c10::nullopt,
               c10::optional<std::vector<at::Tensor>> gate_up_s = c10::nullopt,
-              c10::optional<std::vector<at::Tensor>> down_s = c10::nullopt, bool activations_fp8 = false)
+              c10::optional<std::vector<at::Tensor>> down_s = c10::nullopt, bool activations_fp8 = false,
+              c10::optional<std::vector<at::Tensor>> qkv_z = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> o_z = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> gate_up_z = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> down_z = c10::nullopt)
       : embed_(embed), qkv_w_(qkv_w), o_w_(o_w), gate_up_w_(gate_up_w), down_w_(down_w), in_norm_(in_norm),
         post_norm_(post_norm), final_norm_(final_norm), lm_head_(lm_head), kc_(k_caches), vc_(v_caches),
         cos_sin_(cos_sin), hq_(hq), hkv_(hkv), d_(head_dim), eps_(eps), scale_(scale), vocab_(vocab_size),
@@ -157,7 +161,55 @@ class LlamaRunner {
       w8_ = given == 4;
       const std::vector<at::Tensor>* wl[4] = {&qkv_w_, &o_w_, &gate_up_w_, &down_w_};
       const char* names[4] = {"qkv_w", "o_w", "gate_up_w", "down_w"};
-      if (w8_) {
+      // int4 group-quantised projection weights (W4A16, gemm_w4.hip): the four lists of uint8
+      // zero points [N, K / G] come with the scale lists (then f32 [N, K / G]); the layers run
+      // the same plain sequence as fp8 weights, every projection through linear_w4
+      const c10::optional<std::vector<at::Tensor>>* zl[4] = {&qkv_z, &o_z, &gate_up_z, &down_z};
+      int zgiven = 0;
+      for (auto* p : zl) zgiven += p->has_value() && !(*p)->empty();
+      TORCH_CHECK(zgiven == 0 || (zgiven == 4 && w8_),
+                  "LlamaRunner: the zero points qkv_z, o_z, gate_up_z and down_z are given together, with the four "
+                  "weight scale lists, or not at all");
+      w4_ = zgiven == 4;
+      if (w4_) {
+        TORCH_CHECK(!activations_fp8, "LlamaRunner: fp8 activations need fp8 weights, not int4");
+        qkv_s_ = *qkv_s;
+        o_s_ = *o_s;
+        gate_up_s_ = *gate_up_s;
+        down_s_ = *down_s;
+        qkv_z_ = *qkv_z;
+        o_z_ = *o_z;
+        gate_up_z_ = *gate_up_z;
+        down_z_ = *down_z;
+        const std::vector<at::Tensor>* ss[4] = {&qkv_s_, &o_s_, &gate_up_s_, &down_s_};
+        const std::vector<at::Tensor>* zs[4] = {&qkv_z_, &o_z_, &gate_up_z_, &down_z_};
+        int64_t wsz = 0;
+        for (int k = 0; k < 4; ++k) {
+          TORCH_CHECK(ss[k]->size() == L && zs[k]->size() == L, "LlamaRunner: one ", names[k],
+                      " scale and zero-point tensor per layer");
+          for (size_t l = 0; l < L; ++l) {
+            const at::Tensor& w = (*wl[k])[l];
+            const at::Tensor& sc = (*ss[k])[l];
+            const at::Tensor& zp = (*zs[k])[l];
+            TORCH_CHECK(w4_supported(w), "LlamaRunner: layers.", l, ".", names[k],
+                        " is not a contiguous uint8 [N, K / 2] with N % 64 == 0 and K % 64 == 0 (shape ", w.sizes(),
+                        ", ", w.scalar_type(), "): the W4 kernels do not take it");
+            const int64_t N = w.size(0), K = 2 * w.size(1);
+            TORCH_CHECK(sc.is_cuda() && sc.device() == w.device() && sc.scalar_type() == at::kFloat &&
+                            sc.is_contiguous() && sc.dim() == 2 && sc.size(0) == N && sc.size(1) >= 1 &&
+                            K % sc.size(1) == 0 && (K / sc.size(1)) % 64 == 0,
+                        "LlamaRunner: the scale of layers.", l, ".", names[k], " must be a contiguous float32 [", N,
+                        ", K / G] on the device of the weight, G a multiple of 64 that divides K = ", K);
+            TORCH_CHECK(zp.is_cuda() && zp.device() == w.device() && zp.scalar_type() == at::kByte &&
+                            zp.is_contiguous() && zp.sizes() == sc.sizes(),
+                        "LlamaRunner: the zero points of layers.", l, ".", names[k],
+                        " must be a contiguous uint8 tensor with the shape of the scale");
+            wsz = std::max(wsz, w4_gemm_workspace(int64_t(1) << 20, N, K));
+          }
+        }
+        // split-K partials of w4_gemm, sized once for every row count so graph captures never allocate
+        w8_ws_ = at::empty({std::max<int64_t>(wsz / 4, 4)}, embed_.options().dtype(at::kFloat));
+      } else if (w8_) {
         qkv_s_ = *qkv_s;
         o_s_ = *o_s;
         gate_up_s_ = *gate_up_s;
@@ -355,16 +407,19 @@ class LlamaRunner {
   // linear_w8.  T <= 4 keeps the W8A16 GEMV: it streams each weight byte once and is
   // bandwidth-bound there, so FP8 activations would add a quantiser launch and buy nothing.
   bool a8_route(int64_t T, const at::Tensor& w) const { return a8_ && T > 4 && w8a8_supported(w); }
-  at::Tensor proj_w8(const at::Tensor& x, const at::Tensor& w, const at::Tensor& s) {
+  // int4 weights (w4_): z holds the layer's zero points and every row count goes through
+  // linear_w4 (gemm_w4.hip): w4_gemv at T <= 4 where its shape rule holds, else w4_gemm.
+  at::Tensor proj_w8(const at::Tensor& x, const at::Tensor& w, const at::Tensor& s, const at::Tensor& z) {
     at::Tensor out = at::empty({x.size(0), w.size(0)}, x.options());
-    if (a8_route(x.size(0), w)) linear_w8a8(out, x, w, s, w8_ws_, 0);
+    if (w4_) linear_w4(out, x, w, s, z, w8_ws_, 0);
+    else if (a8_route(x.size(0), w)) linear_w8a8(out, x, w, s, w8_ws_, 0);
     else linear_w8(out, x, w, s, w8_ws_, 0);
     return out;
   }
   // down projection of the SwiGLU: bf16(silu(g) * u) of gu [T, 2F] times w.  With fp8
   // activations the quantiser forms the product itself (silu_mul mode) and the [T, F] bf16
   // intermediate never goes to memory.
-  at::Tensor proj_w8_silu(const at::Tensor& gu, const at::Tensor& w, const at::Tensor& s) {
+  at::Tensor proj_w8_silu(const at::Tensor& gu, const at::Tensor& w, const at::Tensor& s, const at::Tensor& z) {
     const int64_t T = gu.size(0), F = gu.size(1) / 2;
     if (a8_route(T, w)) {
       at::Tensor out = at::empty({T, w.size(0)}, gu.options());
@@ -376,7 +431,7 @@ class LlamaRunner {
     }
     at::Tensor a = at::empty({T, F}, gu.options());
     silu_and_mul(a, gu);
-    return proj_w8(a, w, s);
+    return proj_w8(a, w, s, z);
   }
 
   // silu(x . w[:F]^T) * (x . w[F:]^T) for any row count (same routing as proj)
@@ -494,16 +549,18 @@ class LlamaRunner {
       fused_add_rmsnorm(dn, residual, final_norm_, eps_);
       x = dn;
     }
-    // fp8 projection weights: the plain sequence on the W8 kernels (gemm_w8.hip) -- no fused
-    // GEMV layer, no RoPE inside the GEMM or the attention, no bf16 projection kernel
+    // fp8 or int4 projection weights: the plain sequence on the W8 kernels (gemm_w8.hip) or the
+    // W4 kernels (gemm_w4.hip) -- no fused GEMV layer, no RoPE inside the GEMM or the attention,
+    // no bf16 projection kernel
+    const at::Tensor noz;
     for (int64_t l = 0; l < L && w8_; ++l) {
-      at::Tensor qkv = proj_w8(x, qkv_w_[l], qkv_s_[l]);
+      at::Tensor qkv = proj_w8(x, qkv_w_[l], qkv_s_[l], w4_ ? qkv_z_[l] : noz);
       at::Tensor attn = attend(l, qkv, false);
-      at::Tensor o = proj_w8(attn, o_w_[l], o_s_[l]);
+      at::Tensor o = proj_w8(attn, o_w_[l], o_s_[l], w4_ ? o_z_[l] : noz);
       all_reduce(o);
       fused_add_rmsnorm(o, residual, post_norm_[l], eps_);
-      at::Tensor gu = proj_w8(o, gate_up_w_[l], gate_up_s_[l]);
-      at::Tensor dn = proj_w8_silu(gu, down_w_[l], down_s_[l]);
+      at::Tensor gu = proj_w8(o, gate_up_w_[l], gate_up_s_[l], w4_ ? gate_up_z_[l] : noz);
+      at::Tensor dn = proj_w8_silu(gu, down_w_[l], down_s_[l], w4_ ? down_z_[l] : noz);
       all_reduce(dn);
       fused_add_rmsnorm(dn, residual, l + 1 < L ? in_norm_[l + 1] : final_norm_, eps_);
       x = dn;
@@ -845,7 +902,9 @@ class LlamaRunner {
   std::vector<at::Tensor> q_norm_, k_norm_;   // per-layer [D] weights of the q / k head norm, empty without
   bool qknorm_ = false;
   std::vector<at::Tensor> qkv_s_, o_s_, gate_up_s_, down_s_;   // per-layer f32 row scales of fp8 weights, empty without
-  bool w8_ = false;            // the four projections of every layer are float8_e4m3fn codes + scales
+  bool w8_ = false;            // the four projections of every layer are quantised: fp8 codes + row scales, or int4 (w4_)
+  std::vector<at::Tensor> qkv_z_, o_z_, gate_up_z_, down_z_;   // per-layer uint8 zero points of int4 weights, empty without
+  bool w4_ = false;            // the projections are 4-bit codes with f32 scales and zero points [N, K / G]
   at::Tensor w8_ws_;           // split-K workspace of w8_gemm / w8a8_gemm
   bool a8_ = false;            // fp8 activations: T > 4 projections on the W8A8 kernels (gemm_w8a8.hip)
   c10::optional<at::Tensor> q_norm(int64_t l) const {
@@ -1479,7 +1538,9 @@ void bind_runners(py::module_& m) {
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<int64_t>>,
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
-                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>, bool>(),
+                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>, bool,
+                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
+                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>>(),
            py::arg("embed"), py::arg("qkv_w"), py::arg("o_w"), py::arg("gate_up_w"), py::arg("down_w"),
            py::arg("in_norm"), py::arg("post_norm"), py::arg("final_norm"), py::arg("lm_head"), py::arg("k_caches"),
            py::arg("v_caches"), py::arg("cos_sin"), py::arg("hq"), py::arg("hkv"), py::arg("head_dim"),
@@ -1488,7 +1549,8 @@ void bind_runners(py::module_& m) {
            py::arg("qkv_b") = py::none(), py::arg("windows") = py::none(),
            py::arg("q_norm") = py::none(), py::arg("k_norm") = py::none(), py::arg("qkv_s") = py::none(),
            py::arg("o_s") = py::none(), py::arg("gate_up_s") = py::none(), py::arg("down_s") = py::none(),
-           py::arg("activations_fp8") = false)
+           py::arg("activations_fp8") = false, py::arg("qkv_z") = py::none(), py::arg("o_z") = py::none(),
+           py::arg("gate_up_z") = py::none(), py::arg("down_z") = py::none())
       .def("forward", &LlamaRunner::forward, py::call_guard<py::gil_scoped_release>());
   py::class_<BertRunner>(m, "BertRunner")
       .def(py::init<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<std::vector<at::Tensor>>,

@@ -64,6 +64,76 @@ def linear_w8(x, codes, s, dtype=None):
     return y
 
 
+# ---- int4 group-quantised projection weights (opt-in, W4A16; the AWQ / GPTQ family).  A
+# quantised projection is a triple: codes uint8 [N, K / 2] (two unsigned 4-bit codes q in
+# 0..15 per byte), scale f32 [N, K / G] (positive, finite) and zero uint8 [N, K / G] (0..15),
+# with the group size G = K / scale.shape[1], G % 64 == 0 (G = K: one group per row);
+#   w[n, k] = scale[n, k // G] * (q[n, k] - zero[n, k // G])
+#   y[m, n] = bf16(sum_g scale[n, g] * (sum_{k in g} f32(x[m, k]) * (q[n, k] - zero[n, g])))
+# The integer difference is exact in the multiply, the scale is applied in f32, the sums are f32.
+#
+# NIBBLE ORDER: every aligned 4-byte word of a row holds 8 codes adjacent along K; byte b of
+# the word is q[b] | q[b + 4] << 4.  `word & 0x0F0F0F0F` is then codes 0..3 as four bytes and
+# `(word >> 4) & 0x0F0F0F0F` codes 4..7: the kernel (ops/csrc/gemm_w4.hip w4_unpack8) turns
+# each into a float with one byte-select conversion.
+INT4_GROUP = 128
+
+
+def pack_weight_int4(q):
+    """Codes q [N, K] (integers 0..15, K % 8 == 0) -> uint8 [N, K / 2] in the order above."""
+    N, K = q.shape
+    assert K % 8 == 0 and int(q.min()) >= 0 and int(q.max()) <= 15
+    w = q.to(torch.uint8).view(N, K // 8, 2, 4)            # [.., half, b]: code 4 * half + b
+    return (w[:, :, 0] | (w[:, :, 1] << 4)).reshape(N, K // 2).contiguous()
+
+
+def unpack_weight_int4(codes):
+    """uint8 [N, K / 2] -> codes uint8 [N, K] (the inverse of pack_weight_int4)."""
+    N, K2 = codes.shape
+    w = codes.view(N, K2 // 4, 1, 4)
+    return torch.cat([w & 15, w >> 4], 2).reshape(N, 2 * K2)
+
+
+def quantize_weight_int4(w, group: int = INT4_GROUP):
+    """(codes, scale, zero) of a [N, K] weight (any float dtype), asymmetric min / max per
+    group with 0 inside the range: scale = (max - min) / 15 in f32 (1 for an all-zero group),
+    zero = RNE(-min / scale), q = clamp(RNE(w / scale) + zero, 0, 15).  ``group`` <= 0 or
+    >= K: one group per row."""
+    N, K = w.shape
+    G = K if group <= 0 or group >= K else group
+    if K % G or G % 64:
+        raise ValueError(f"int4 group size {G} must be a multiple of 64 that divides K = {K}")
+    wf = w.float().view(N, K // G, G)
+    lo, hi = wf.amin(2).clamp(max=0.0), wf.amax(2).clamp(min=0.0)
+    scale = torch.where(hi > lo, (hi - lo) / 15.0, torch.ones_like(hi)).to(torch.float32)
+    zero = torch.round(-lo / scale).clamp(0, 15)
+    q = (torch.round(wf / scale[:, :, None]) + zero[:, :, None]).clamp(0, 15)
+    return pack_weight_int4(q.view(N, K)), scale.contiguous(), zero.to(torch.uint8).contiguous()
+
+
+def dequantize_weight_int4(codes, scale, zero, dtype=torch.float32):
+    """scale * (q - zero) as `dtype` [N, K] (f32: exact up to one rounding of the product)."""
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    NG = scale.shape[1]
+    d = unpack_weight_int4(codes).to(dtype).view(N, NG, K // NG) - zero.to(dtype)[:, :, None]
+    return (d * scale.to(dtype)[:, :, None]).view(N, K)
+
+
+def linear_w4(x, codes, scale, zero, dtype=None):
+    """The W4A16 projection on the CPU and the oracle: per group the partial sum of
+    x * (q - zero), scaled once, accumulated in f32 (or `dtype`, e.g. float64); returns x's
+    dtype for bf16 / f16 x, else the compute dtype."""
+    ct = dtype or torch.float32
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    NG = scale.shape[1]
+    d = unpack_weight_int4(codes).to(ct).view(N, NG, K // NG) - zero.to(ct)[:, :, None]
+    part = torch.einsum("mgk,ngk->mng", x.to(ct).view(x.shape[0], NG, K // NG), d)
+    y = (part * scale.to(ct)[None]).sum(2)
+    if dtype is None and x.dtype in (torch.bfloat16, torch.float16):
+        return y.to(x.dtype)
+    return y
+
+
 # ---- fp8 activations (opt-in, W8A8).  Each row of a projection's input is quantised on the
 # fly: xs[m] = max_k |x[m, k]| / 448 in f32 (1 for a zero row), inv = 1.0f / xs[m],
 # code = e4m3fn(RNE(clamp(f32(x) * inv, -448, 448))); then

@@ -21,7 +21,9 @@ Configuration (``local-gpu-configuration`` resource):
   weights-dtype (auto | bf16 | fp8; unset: the LS_WEIGHTS_DTYPE environment variable, else auto.
   auto: what the checkpoint holds, bf16 for presets; fp8 on a bf16 checkpoint or preset quantises
   the four projections of every layer at load, e4m3 codes with one scale per output row; bf16 on an
-  fp8 checkpoint is refused),
+  fp8 checkpoint is refused.  An AWQ or GPTQ checkpoint holds int4 weights -- 4-bit codes with a scale
+  and a zero point per group of input columns -- and is served as such under auto; bf16 and fp8 on it
+  are refused),
   activations-dtype (bf16 | fp8; unset: the LS_ACTIVATIONS_DTYPE environment variable, else bf16.
   fp8 needs fp8 weights: steps of more than 4 rows quantise each projection's input rows to e4m3
   with one dynamic scale per row and run on the FP8 matrix instructions; never set by a checkpoint),
@@ -177,6 +179,12 @@ class ServiceRegistry:
                 if wd == "bf16" and held == "fp8":
                     raise ValueError("weights-dtype bf16: the checkpoint holds fp8 (float8_e4m3fn) projection "
                                      "weights, which are not widened; use auto or fp8")
+                if wd == "bf16" and held == "int4":
+                    raise ValueError("weights-dtype bf16: the checkpoint holds int4 (AWQ / GPTQ) projection "
+                                     "weights, which are not widened; use auto")
+                if wd == "fp8" and held == "int4":
+                    raise ValueError("weights-dtype fp8: the checkpoint holds int4 (AWQ / GPTQ) projection "
+                                     "weights, which are not requantised; use auto")
                 wd = held if wd == "auto" else wd
                 if self.tp is not None and self.tp.world > 1:
                     sd = shard_llama(sd, mcfg, self.tp.rank, self.tp.world)
