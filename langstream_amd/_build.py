@@ -96,9 +96,9 @@ def build_hip(verbose: bool = False) -> str:
         "-Wno-unused-result", "-Wno-deprecated-declarations", "-Wno-unused-command-line-argument",
         "-fgpu-rdc" if False else "-fno-gpu-rdc",
     ]
-    # per-source extras: gemm_w8a8.hip and gemm_w4.hip are compiled without the packed-f32 VALU forms
+    # per-source extras: gemm_w8a8.hip, gemm_w4.hip and moe.hip are compiled without the packed-f32 VALU forms
     no_pk = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-    extra = {"gemm_w8a8.hip": no_pk, "gemm_w4.hip": no_pk}
+    extra = {"gemm_w8a8.hip": no_pk, "gemm_w4.hip": no_pk, "moe.hip": no_pk}
     jobs = []
     objs = []
     for s in srcs:

@@ -56,6 +56,14 @@ class LlamaConfig:
     # None with a window: every layer
     sliding_window: int = 0
     window_layers: Optional[tuple] = None
+    # sparse mixture-of-experts MLP (Qwen3-MoE, Mixtral): num_experts experts of width
+    # moe_intermediate_size per layer, each token routed to experts_per_token of them by a
+    # softmax router; norm_topk_prob: the selected weights are renormalised to sum 1.
+    # num_experts = 0: the dense MLP of width intermediate_size
+    num_experts: int = 0
+    experts_per_token: int = 0
+    moe_intermediate_size: int = 0
+    norm_topk_prob: bool = False
 
     def layer_window(self, i: int) -> int:
         """The attention window of layer i (0: full attention)."""
@@ -71,6 +79,8 @@ class LlamaConfig:
         qkv = H * (self.num_heads + 2 * self.num_kv_heads) * self.head_dim
         o = self.num_heads * self.head_dim * H
         mlp = 3 * H * Fi
+        if self.num_experts:   # every expert and the router
+            mlp = self.num_experts * (3 * H * self.moe_intermediate_size + H)
         if self.qkv_bias:
             qkv += (self.num_heads + 2 * self.num_kv_heads) * self.head_dim
         if self.qk_norm:
@@ -80,8 +90,11 @@ class LlamaConfig:
     def flops_per_token(self, ctx: int = 0) -> float:
         """Forward FLOPs per token (2 * matmul params + attention)."""
         H, Fi, L = self.hidden_size, self.intermediate_size, self.num_layers
+        mlp = 3 * H * Fi
+        if self.num_experts:   # the active experts and the router
+            mlp = self.experts_per_token * 3 * H * self.moe_intermediate_size + self.num_experts * H
         lin = 2 * L * (H * (self.num_heads + 2 * self.num_kv_heads) * self.head_dim
-                       + self.num_heads * self.head_dim * H + 3 * H * Fi) + 2 * self.vocab_size * H
+                       + self.num_heads * self.head_dim * H + mlp) + 2 * self.vocab_size * H
         attn = 4 * L * self.num_heads * self.head_dim * ctx
         return float(lin + attn)
 
@@ -124,6 +137,22 @@ PRESETS = {
                             num_layers=36, num_heads=32, num_kv_heads=8, head_dim=128, max_position=40960,
                             bos_token_id=151643, eos_token_ids=(151645, 151643), qk_norm=True, rope_theta=1e6,
                             rms_eps=1e-6),
+    # Qwen3-MoE: Qwen3's attention, a routed MLP in every layer.  qwen3-moe-tiny is qwen3-tiny with
+    # 8 experts of width 128, two per token
+    "qwen3-moe-tiny": LlamaConfig(name="qwen3-moe-tiny", vocab_size=512, hidden_size=256, intermediate_size=512,
+                                  num_layers=2, num_heads=4, num_kv_heads=2, head_dim=64, max_position=2048,
+                                  bos_token_id=1, eos_token_ids=(2,), qk_norm=True, rope_theta=1e6, rms_eps=1e-6,
+                                  num_experts=8, experts_per_token=2, moe_intermediate_size=128,
+                                  norm_topk_prob=True),
+    "qwen3-30b-a3b": LlamaConfig(name="qwen3-30b-a3b", vocab_size=151936, hidden_size=2048, intermediate_size=6144,
+                                 num_layers=48, num_heads=32, num_kv_heads=4, head_dim=128, max_position=40960,
+                                 bos_token_id=151643, eos_token_ids=(151645, 151643), qk_norm=True, rope_theta=1e6,
+                                 rms_eps=1e-6, num_experts=128, experts_per_token=8, moe_intermediate_size=768,
+                                 norm_topk_prob=True),
+    "mixtral-8x7b": LlamaConfig(name="mixtral-8x7b", vocab_size=32000, hidden_size=4096, intermediate_size=14336,
+                                num_layers=32, num_heads=32, num_kv_heads=8, head_dim=128, max_position=32768,
+                                rope_theta=1e6, bos_token_id=1, eos_token_ids=(2,), num_experts=8,
+                                experts_per_token=2, moe_intermediate_size=14336, norm_topk_prob=True),
 }
 
 
@@ -246,8 +275,18 @@ class LlamaLayer:
         mk = lambda *s: (torch.randn(*s, device=device, dtype=torch.float32) * std).to(dtype)  # noqa: E731
         self.qkv_w = mk((self.hq + 2 * self.hkv) * D, H)
         self.o_w = mk(H, self.hq * D) / math.sqrt(2 * cfg.num_layers)
-        self.gate_up_w = mk(2 * self.f, H)
-        self.down_w = mk(H, self.f) / math.sqrt(2 * cfg.num_layers)
+        # a mixture-of-experts layer holds the router and the stacked expert weights instead
+        # of gate_up_w / down_w: gate_up [E, 2F, H] (an expert's gate rows, then its up rows)
+        self.moe = cfg.num_experts > 0
+        self.gate_up_w = self.down_w = self.router_w = self.experts_gate_up_w = self.experts_down_w = None
+        if self.moe:
+            E, Fm = cfg.num_experts, cfg.moe_intermediate_size
+            self.router_w = mk(E, H)
+            self.experts_gate_up_w = mk(E, 2 * Fm, H)
+            self.experts_down_w = mk(E, H, Fm) / math.sqrt(2 * cfg.num_layers)
+        else:
+            self.gate_up_w = mk(2 * self.f, H)
+            self.down_w = mk(H, self.f) / math.sqrt(2 * cfg.num_layers)
         # fp8 weights: codes + one f32 scale per output row, quantised here, layer by layer,
         # so the model never exists in full at the wider type
         self.qkv_s = self.o_s = self.gate_up_s = self.down_s = None
@@ -275,7 +314,8 @@ class LlamaLayer:
         self.k_norm = torch.ones(D, device=device, dtype=dtype) if cfg.qk_norm else None
 
     def tensors(self):
-        t = [self.qkv_w, self.o_w, self.gate_up_w, self.down_w, self.in_norm, self.post_norm]
+        mlp = [self.router_w, self.experts_gate_up_w, self.experts_down_w] if self.moe else [self.gate_up_w, self.down_w]
+        t = [self.qkv_w, self.o_w, *mlp, self.in_norm, self.post_norm]
         if self.qkv_s is not None:
             t += [self.qkv_s, self.o_s, self.gate_up_s, self.down_s]
         if self.qkv_z is not None:
@@ -296,6 +336,19 @@ class LlamaModel:
             raise ValueError(f"weights_dtype must be one of {WEIGHTS_DTYPES}, got {weights_dtype!r}")
         if activations_dtype not in ACTIVATIONS_DTYPES:
             raise ValueError(f"activations_dtype must be one of {ACTIVATIONS_DTYPES}, got {activations_dtype!r}")
+        if cfg.num_experts:
+            # refused by name, never silently served
+            if weights_dtype != "bf16" or activations_dtype != "bf16":
+                raise ValueError(f"a mixture-of-experts model ({cfg.name}) with fp8 or int4 weights or fp8 activations "
+                                 f"is not supported: quantised experts have no kernel yet")
+            if tp is not None and tp.world > 1:
+                raise ValueError(f"a mixture-of-experts model ({cfg.name}) under tensor parallelism (world "
+                                 f"{tp.world}) is not supported: the experts are not sharded yet")
+            if not ops.moe_supported(cfg.hidden_size, cfg.moe_intermediate_size, cfg.num_experts,
+                                     cfg.experts_per_token):
+                raise ValueError(f"{cfg.name}: hidden {cfg.hidden_size}, expert width {cfg.moe_intermediate_size}, "
+                                 f"{cfg.num_experts} experts, {cfg.experts_per_token} per token is outside the MoE "
+                                 f"shape rule (H % 64 == 0, F % 64 == 0, E <= 256, 1 <= k <= min(E, 16))")
         if activations_dtype == "fp8" and weights_dtype != "fp8":
             raise ValueError("activations_dtype='fp8' needs weights_dtype='fp8': both operands go to the FP8 "
                              "matrix unit")
@@ -352,7 +405,8 @@ class LlamaModel:
 
     # ------------------------------------------------------------------ weights io
     def _layer_names(self) -> tuple:
-        names = ("qkv_w", "o_w", "gate_up_w", "down_w", "in_norm", "post_norm")
+        mlp = ("router_w", "experts_gate_up_w", "experts_down_w") if self.cfg.num_experts else ("gate_up_w", "down_w")
+        names = ("qkv_w", "o_w", *mlp, "in_norm", "post_norm")
         if self.cfg.qkv_bias:
             names += ("qkv_b",)
         if self.cfg.qk_norm:
@@ -485,7 +539,11 @@ class LlamaModel:
             o = _linear(attn, layer.o_w, layer.o_s, a8, layer.o_z)
             self.tp.all_reduce(o)
             ops.fused_add_rmsnorm(o, residual, layer.post_norm, eps)
-            if layer.gate_up_s is not None:
+            if layer.moe:
+                d = ops.moe_mlp(o, layer.router_w, layer.experts_gate_up_w, layer.experts_down_w,
+                                cfg.experts_per_token, cfg.norm_topk_prob)
+                a = None
+            elif layer.gate_up_s is not None:
                 gu = _linear(o, layer.gate_up_w, layer.gate_up_s, a8, layer.gate_up_z)
                 if _a8(gu, layer.down_w, a8):
                     # the quantiser forms bf16(silu(g) * u) itself: no [T, F] intermediate
@@ -515,11 +573,12 @@ class LlamaModel:
             return r[1]
         L = self.layers
         pg = None
+        moe = self.cfg.num_experts > 0
         if self.tp.world > 1 or self.tp.force_pg:
             pg = self.tp.group if self.tp.group is not None else dist.group.WORLD
         runner = ops.hip().LlamaRunner(
-            self.embed, [l.qkv_w for l in L], [l.o_w for l in L], [l.gate_up_w for l in L],
-            [l.down_w for l in L], [l.in_norm for l in L], [l.post_norm for l in L], self.final_norm,
+            self.embed, [l.qkv_w for l in L], [l.o_w for l in L], [] if moe else [l.gate_up_w for l in L],
+            [] if moe else [l.down_w for l in L], [l.in_norm for l in L], [l.post_norm for l in L], self.final_norm,
             self.lm_head, [kv[0] for kv in kv_caches], [kv[1] for kv in kv_caches], self.cos_sin, self.hq,
             self.hkv, self.cfg.head_dim, self.cfg.rms_eps, self.scale, self.cfg.vocab_size, self.vocab_start, pg,
             self.kv_k_scale, self.kv_v_scale, [l.qkv_b for l in L] if self.cfg.qkv_bias else None,
@@ -528,7 +587,10 @@ class LlamaModel:
             [l.k_norm for l in L] if self.cfg.qk_norm else None,
             *([[getattr(l, n + "_s") for l in L] for n in W8_NAMES] if self.weights_dtype in ("fp8", "int4") else []),
             activations_fp8=self.activations_dtype == "fp8",
-            **({n + "_z": [getattr(l, n + "_z") for l in L] for n in W8_NAMES} if self.weights_dtype == "int4" else {}))
+            **({n + "_z": [getattr(l, n + "_z") for l in L] for n in W8_NAMES} if self.weights_dtype == "int4" else {}),
+            **(dict(router_w=[l.router_w for l in L], experts_gate_up_w=[l.experts_gate_up_w for l in L],
+                    experts_down_w=[l.experts_down_w for l in L], experts_per_token=self.cfg.experts_per_token,
+                    norm_topk=self.cfg.norm_topk_prob) if moe else {}))
         self._runner = (key, runner, kv_caches)
         return runner
 

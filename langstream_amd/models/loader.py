@@ -66,7 +66,9 @@ def load_packed(path: str, device="cpu") -> Dict[str, torch.Tensor]:
 # ---------------------------------------------------------------- Llama
 
 
-HF_MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")   # Llama-architecture families the engine serves
+# Llama-architecture families the engine serves; the last two have a mixture-of-experts MLP
+HF_MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3", "qwen3_moe", "mixtral")
+MOE_MODEL_TYPES = ("qwen3_moe", "mixtral")
 
 
 def hf_model_type(model_dir: str) -> str:
@@ -154,11 +156,44 @@ def _window_layers_from_hf(c: dict, mtype: str) -> Optional[tuple]:
         if len(lt) != n:
             raise ValueError(f"layer_types has {len(lt)} entries for {n} layers")
         layers = tuple(i for i, t in enumerate(lt) if t == "sliding_attention")
-    elif mtype in ("qwen2", "qwen3"):
+    elif mtype in ("qwen2", "qwen3", "qwen3_moe"):
         layers = tuple(range(min(int(c.get("max_window_layers", 28)), n), n))
     else:
         return None
     return None if len(layers) == n else layers
+
+
+def _moe_from_hf(c: dict, mtype: str) -> dict:
+    """The mixture-of-experts fields of a ``qwen3_moe`` / ``mixtral`` config ({} for a dense
+    family).  Every layer must be sparse and nothing but routed experts may feed the MLP
+    output; a config that says otherwise is refused by the name of its key."""
+    if mtype not in MOE_MODEL_TYPES:
+        return {}
+    # the expert count goes by either name, whatever the family (the library writes both forms)
+    ekey = "num_experts" if c.get("num_experts") else "num_local_experts"
+    for key in (ekey, "num_experts_per_tok"):
+        if not c.get(key):
+            raise ValueError(f"model_type {mtype!r}: config.json has no "
+                             f"{'num_experts / num_local_experts' if key == ekey else key}")
+    if c.get("decoder_sparse_step", 1) != 1:
+        raise ValueError(f"decoder_sparse_step = {c['decoder_sparse_step']!r}: only models whose every layer is a "
+                         f"mixture of experts are supported (decoder_sparse_step = 1)")
+    if c.get("mlp_only_layers"):
+        raise ValueError(f"mlp_only_layers = {c['mlp_only_layers']!r}: dense layers inside a mixture-of-experts "
+                         f"model are not supported")
+    for key in ("shared_expert_intermediate_size", "n_shared_experts", "num_shared_experts"):
+        if c.get(key):
+            raise ValueError(f"{key} = {c[key]!r}: shared experts are not supported")
+    if c.get("quantization_config"):
+        raise ValueError("quantization_config: a quantised mixture-of-experts checkpoint is not supported "
+                         "(bf16 / f16 / f32 experts only)")
+    F = c.get("moe_intermediate_size") if mtype == "qwen3_moe" else c.get("intermediate_size")
+    if not F:
+        raise ValueError(f"model_type {mtype!r}: config.json has no "
+                         f"{'moe_intermediate_size' if mtype == 'qwen3_moe' else 'intermediate_size'}")
+    return dict(num_experts=int(c[ekey]), experts_per_token=int(c["num_experts_per_tok"]),
+                moe_intermediate_size=int(F),
+                norm_topk_prob=True if mtype == "mixtral" else bool(c.get("norm_topk_prob", False)))
 
 
 def llama_config_from_hf(model_dir: str, sliding_window: bool = False) -> LlamaConfig:
@@ -183,10 +218,11 @@ def llama_config_from_hf(model_dir: str, sliding_window: bool = False) -> LlamaC
     if mtype not in HF_MODEL_TYPES:
         raise ValueError(f"unsupported model_type {mtype!r} (supported: {', '.join(HF_MODEL_TYPES)})")
     theta, scaling = _rope_from_hf(c)
+    moe = _moe_from_hf(c, mtype)
     names = _checkpoint_names(model_dir)
     _check_quantization_config(c, names)
     qkv_bias = mtype == "qwen2" or any(n.endswith("self_attn.q_proj.bias") for n in names)
-    qk_norm = mtype == "qwen3" or any(n.endswith("self_attn.q_norm.weight") for n in names)
+    qk_norm = mtype in ("qwen3", "qwen3_moe") or any(n.endswith("self_attn.q_norm.weight") for n in names)
     max_pos = c.get("max_position_embeddings", 8192)
     for t in c.get("layer_types") or ():
         if t not in LAYER_TYPES:
@@ -194,7 +230,7 @@ def llama_config_from_hf(model_dir: str, sliding_window: bool = False) -> LlamaC
     # an active sliding window: full attention equals windowed attention up to the window,
     # so positions past it are not served
     window = c.get("sliding_window")
-    if mtype in ("qwen2", "qwen3") and not c.get("use_sliding_window", False):
+    if mtype in ("qwen2", "qwen3", "qwen3_moe") and not c.get("use_sliding_window", False):
         window = None
     if mtype == "llama":
         window = None
@@ -220,7 +256,7 @@ def llama_config_from_hf(model_dir: str, sliding_window: bool = False) -> LlamaC
     bos = c.get("bos_token_id")
     return LlamaConfig(
         name=c.get("_name_or_path") or mtype, vocab_size=c["vocab_size"], hidden_size=c["hidden_size"],
-        intermediate_size=c["intermediate_size"], num_layers=c["num_hidden_layers"],
+        intermediate_size=c.get("intermediate_size") or moe["moe_intermediate_size"], num_layers=c["num_hidden_layers"],
         num_heads=c["num_attention_heads"],
         num_kv_heads=c.get("num_key_value_heads") or c["num_attention_heads"],
         head_dim=c.get("head_dim") or c["hidden_size"] // c["num_attention_heads"],
@@ -228,7 +264,7 @@ def llama_config_from_hf(model_dir: str, sliding_window: bool = False) -> LlamaC
         rms_eps=c.get("rms_norm_eps", 1e-5), max_position=max_pos,
         tie_embeddings=bool(c.get("tie_word_embeddings", False)), bos_token_id=1 if bos is None else bos,
         eos_token_ids=tuple(eos), qkv_bias=qkv_bias, qk_norm=qk_norm, sliding_window=win,
-        window_layers=win_layers)
+        window_layers=win_layers, **moe)
 
 
 AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)   # nibble i of an AWQ word holds column 8 * col + AWQ_ORDER[i]
@@ -400,8 +436,9 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = N
             out[f"layers.{i}.q_norm"] = take(qn)
             out[f"layers.{i}.k_norm"] = take(kn)
         fuse(f"layers.{i}.o", [p + "self_attn.o_proj"])
-        fuse(f"layers.{i}.gate_up", [p + "mlp.gate_proj", p + "mlp.up_proj"])
-        fuse(f"layers.{i}.down", [p + "mlp.down_proj"])
+        if not _moe_layer(hf, take, out, i):
+            fuse(f"layers.{i}.gate_up", [p + "mlp.gate_proj", p + "mlp.up_proj"])
+            fuse(f"layers.{i}.down", [p + "mlp.down_proj"])
         out[f"layers.{i}.in_norm"] = take(p + "input_layernorm.weight")
         out[f"layers.{i}.post_norm"] = take(p + "post_attention_layernorm.weight")
         i += 1
@@ -421,6 +458,54 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor], cfg: Optional[LlamaConfig] = N
         raise ValueError(f"checkpoint tensor {left[0]!r} is not supported"
                          + (f" (and {len(left) - 1} more)" if len(left) > 1 else ""))
     return out
+
+
+# per-expert hub names of the two MoE families: (block, gate, up, down)
+_MOE_NAMES = (("mlp", "gate_proj", "up_proj", "down_proj"), ("block_sparse_moe", "w1", "w3", "w2"))
+
+
+def _moe_layer(hf, take, out, i: int) -> bool:
+    """The mixture-of-experts MLP of layer i, if the checkpoint has one: the router
+    (``{block}.gate.weight``) and the experts, per expert under the hub names
+    (Qwen3-MoE ``mlp.experts.{e}.gate_proj / up_proj / down_proj.weight``, Mixtral
+    ``block_sparse_moe.experts.{e}.w1 / w3 / w2.weight``) or already stacked
+    (``{block}.experts.gate_up_proj`` [E, 2F, H] and ``.down_proj`` [E, H, F]), become
+    ``router_w`` [E, H], ``experts_gate_up_w`` [E, 2F, H] (gate rows, then up rows) and
+    ``experts_down_w`` [E, H, F].  Quantised experts and shared experts are refused by name."""
+    p = f"model.layers.{i}."
+    for block, gate, up, down in _MOE_NAMES:
+        b = p + block + "."
+        if b + "gate.weight" not in hf:
+            continue
+        for n in hf:
+            if n.startswith(b) and ("shared_expert" in n or n.endswith((".qweight", ".weight_scale", ".scales"))):
+                raise ValueError(f"checkpoint tensor {n!r}: shared experts and quantised experts are not supported")
+        router = take(b + "gate.weight")
+        if b + "experts.gate_up_proj" in hf:
+            gu, dn = take(b + "experts.gate_up_proj"), take(b + "experts.down_proj")
+        else:
+            E = router.shape[0]
+            for e in range(E):
+                for part in (gate, up, down):
+                    if f"{b}experts.{e}.{part}.weight" not in hf:
+                        raise ValueError(f"checkpoint tensor {b}experts.{e}.{part}.weight is missing "
+                                         f"({b}gate.weight routes over {E} experts)")
+            gu = torch.stack([torch.cat([take(f"{b}experts.{e}.{gate}.weight"), take(f"{b}experts.{e}.{up}.weight")], 0)
+                              for e in range(E)])
+            dn = torch.stack([take(f"{b}experts.{e}.{down}.weight") for e in range(E)])
+        E, H = router.shape
+        for n, t in ((b + "experts gate_up", gu), (b + "experts down", dn)):
+            if t.dtype == FP8 or not t.is_floating_point():
+                raise ValueError(f"checkpoint tensors {n} are {t.dtype}: quantised experts are not supported")
+        if gu.dim() != 3 or dn.dim() != 3 or gu.shape[0] != E or dn.shape[0] != E or gu.shape[2] != H or \
+                dn.shape[1] != H or gu.shape[1] != 2 * dn.shape[2]:
+            raise ValueError(f"checkpoint tensors under {b}experts have shapes {tuple(gu.shape)} / {tuple(dn.shape)}, "
+                             f"expected [E, 2F, H] / [E, H, F] with E = {E}, H = {H}")
+        out[f"layers.{i}.router_w"] = router
+        out[f"layers.{i}.experts_gate_up_w"] = gu.contiguous()
+        out[f"layers.{i}.experts_down_w"] = dn.contiguous()
+        return True
+    return False
 
 
 def _cat_rows(ts) -> torch.Tensor:

@@ -253,6 +253,58 @@ def w8_launch_counts(reset: bool = False) -> dict:
     return dict(hip().w8_launch_counts(reset))
 
 
+# ---------------------------------------------------------------- mixture of experts
+def moe_supported(H: int, F: int, E: int, k: int) -> bool:
+    """The shape rule of the MoE kernels (ops/csrc/moe.hip): H % 64 == 0, F % 64 == 0, E <= 256,
+    1 <= k <= min(E, 16).  Anything else is refused by name, never rerouted."""
+    return ref.moe_supported(H, F, E, k)
+
+
+def _moe_check(x, router_w, k: int, F: int = 64) -> None:
+    if not moe_supported(x.shape[1], F, router_w.shape[0], k):
+        raise ValueError(f"mixture of experts with H = {x.shape[1]}, F = {F}, E = {router_w.shape[0]}, k = {k} is "
+                         f"outside the MoE shape rule (H % 64 == 0, F % 64 == 0, E <= 256, 1 <= k <= min(E, 16))")
+
+
+def moe_route(x, router_w, k: int, norm_topk: bool):
+    """Router of a mixture-of-experts layer in one kernel: softmax(x . router_w^T) over the E
+    experts in f32, the k largest per row (the lower index on a tie), renormalised to sum 1
+    with ``norm_topk``.  Returns (topk_ids int32 [T, k], topk_w f32 [T, k]), descending."""
+    _moe_check(x, router_w, k)
+    if _gpu(x, router_w):
+        ids = torch.empty(x.shape[0], k, dtype=torch.int32, device=x.device)
+        w = torch.empty(x.shape[0], k, dtype=torch.float32, device=x.device)
+        hip().moe_route(ids, w, x, router_w, bool(norm_topk))
+        return ids, w
+    return ref.moe_route(x, router_w, k, norm_topk)
+
+
+def moe_mlp(x, router_w, gate_up_w, down_w, k: int, norm_topk: bool, out=None, route=None, tile_rows: int = 0):
+    """Sparse MoE MLP: out[t] = sum over the k routed experts e of topk_w * down_w[e] .
+    (silu(gate_w[e] . x_t) * (up_w[e] . x_t)), with gate_up_w [E, 2F, H] and down_w [E, H, F]
+    (ops/csrc/moe.hip: route, align, two grouped GEMMs, combine; rounding points in
+    ops.reference.moe_mlp).  ``route`` = (topk_ids, topk_w) replaces the router;
+    ``tile_rows`` 32 or 128 forces the row-tile height of the grouped GEMMs (0: the rule)."""
+    _moe_check(x, router_w, k, down_w.shape[2])
+    if _gpu(x, gate_up_w, down_w):
+        ids, w = route if route is not None else moe_route(x, router_w, k, norm_topk)
+        out = torch.empty_like(x) if out is None else out
+        hip().moe_experts(out, x, gate_up_w, down_w, ids, w, tile_rows)
+        return out
+    r = ref.moe_mlp(x, router_w, gate_up_w, down_w, k, norm_topk, route=route)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
+def moe_launch_counts(reset: bool = False) -> dict:
+    """Launches of the MoE kernels since the last reset: "route_mfma" / "route_dot",
+    "align", "gate_up_bm32" / "gate_up_bm128", "down_bm32" / "down_bm128" (the row-tile
+    height of the grouped GEMMs), "combine"."""
+    return dict(hip().moe_launch_counts(reset))
+
+
 def quantize_rows_fp8(x, silu_mul: bool = False):
     """Per-row dynamic FP8 quantisation (ops/csrc/gemm_w8a8.hip): bf16 x [M, K] -> (xq
     float8_e4m3fn [M, K], xs f32 [M]) with xs = amax / 448 (1 for a zero row) and xq =

@@ -113,5 +113,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w4_gemv", &w4_gemv);
   m.def("linear_w4", &linear_w4, py::arg("out"), py::arg("x"), py::arg("w"), py::arg("s"), py::arg("z"),
         py::arg("workspace"), py::arg("splits") = 0);
+  m.def("moe_supported", &moe_supported);
+  m.def("moe_route", &moe_route);
+  m.def("moe_experts", &moe_experts, py::arg("out"), py::arg("x"), py::arg("gate_up_w"), py::arg("down_w"),
+        py::arg("ids"), py::arg("wts"), py::arg("tile_rows") = 0);
+  m.def("moe_launch_counts", &moe_launch_counts, py::arg("reset") = false);
   bind_runners(m);
 }

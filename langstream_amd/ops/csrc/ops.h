@@ -282,5 +282,14 @@ void linear_w4(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s, at::Ten
                int64_t splits_force);
 void w4_launch_counts(pybind11::dict& d, bool reset);   // adds its keys to the census of w8_launch_counts
 
+// ---------------------------------------------------------------------------- moe.hip
+// Sparse mixture-of-experts MLP: router_w [E, H], gate_up_w [E, 2F, H], down_w [E, H, F], all bf16;
+// topk_ids int32 / topk_w f32 [T, k].
+bool moe_supported(int64_t H, int64_t F, int64_t E, int64_t k);
+void moe_route(at::Tensor ids, at::Tensor wts, at::Tensor x, at::Tensor router_w, bool norm_topk);
+void moe_experts(at::Tensor out, at::Tensor x, at::Tensor gate_up_w, at::Tensor down_w, at::Tensor ids,
+                 at::Tensor wts, int64_t tile_rows_force);
+pybind11::dict moe_launch_counts(bool reset);
+
 // -------------------------------------------------------------------------- runner.hip
 void bind_runners(pybind11::module_& m);

@@ -107,12 +107,49 @@ class LlamaRunner {
               c10::optional<std::vector<at::Tensor>> qkv_z = c10::nullopt,
               c10::optional<std::vector<at::Tensor>> o_z = c10::nullopt,
               c10::optional<std::vector<at::Tensor>> gate_up_z = c10::nullopt,
-              c10::optional<std::vector<at::Tensor>> down_z = c10::nullopt)
+              c10::optional<std::vector<at::Tensor>> down_z = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> router_w = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> experts_gate_up_w = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> experts_down_w = c10::nullopt, int64_t experts_per_token = 0,
+              bool norm_topk = false)
       : embed_(embed), qkv_w_(qkv_w), o_w_(o_w), gate_up_w_(gate_up_w), down_w_(down_w), in_norm_(in_norm),
         post_norm_(post_norm), final_norm_(final_norm), lm_head_(lm_head), kc_(k_caches), vc_(v_caches),
         cos_sin_(cos_sin), hq_(hq), hkv_(hkv), d_(head_dim), eps_(eps), scale_(scale), vocab_(vocab_size),
         vocab_start_(vocab_start), k_scale_(k_scale), v_scale_(v_scale) {
     const size_t L = qkv_w_.size();
+    // mixture-of-experts MLP (moe.hip): the per-layer router [E, H], expert gate_up [E, 2F, H] and
+    // expert down [E, H, F] lists are given together or not at all; given, they stand in for
+    // gate_up_w / down_w (then empty) and every layer's MLP is moe_route + moe_experts
+    {
+      const c10::optional<std::vector<at::Tensor>>* ml[3] = {&router_w, &experts_gate_up_w, &experts_down_w};
+      int given = 0;
+      for (auto* p : ml) given += p->has_value() && !(*p)->empty();
+      TORCH_CHECK(given == 0 || given == 3,
+                  "LlamaRunner: router_w, experts_gate_up_w and experts_down_w are given together or not at all");
+      moe_ = given == 3;
+    }
+    if (moe_) {
+      router_w_ = *router_w;
+      xgate_up_w_ = *experts_gate_up_w;
+      xdown_w_ = *experts_down_w;
+      moe_k_ = experts_per_token;
+      moe_norm_ = norm_topk;
+      TORCH_CHECK(gate_up_w_.empty() && down_w_.empty(),
+                  "LlamaRunner: a mixture-of-experts model has no dense gate_up_w / down_w");
+      TORCH_CHECK(router_w_.size() == L && xgate_up_w_.size() == L && xdown_w_.size() == L,
+                  "LlamaRunner: one router and one pair of expert weight stacks per layer");
+      for (size_t l = 0; l < L; ++l) {
+        const at::Tensor &r = router_w_[l], &g = xgate_up_w_[l], &d = xdown_w_[l];
+        TORCH_CHECK(r.dim() == 2 && g.dim() == 3 && d.dim() == 3 && g.size(0) == r.size(0) && d.size(0) == r.size(0) &&
+                        g.size(2) == r.size(1) && d.size(1) == r.size(1) && g.size(1) == 2 * d.size(2),
+                    "LlamaRunner: layers.", l, " expert weights are not router [E, H], gate_up [E, 2F, H], down [E, H, F]");
+        TORCH_CHECK(moe_supported(r.size(1), d.size(2), r.size(0), moe_k_), "LlamaRunner: layers.", l,
+                    " mixture of experts with H = ", r.size(1), ", F = ", d.size(2), ", E = ", r.size(0), ", k = ", moe_k_,
+                    " is outside the MoE shape rule (H % 64 == 0, F % 64 == 0, E <= 256, 1 <= k <= min(E, 16))");
+      }
+      gate_up_w_ = xgate_up_w_;   // placeholders so the per-layer lists keep one entry per layer; never a GEMM operand
+      down_w_ = xdown_w_;
+    }
     TORCH_CHECK(L > 0 && o_w_.size() == L && gate_up_w_.size() == L && down_w_.size() == L &&
                 in_norm_.size() == L && post_norm_.size() == L && kc_.size() == L && vc_.size() == L,
                 "inconsistent layer lists");
@@ -159,6 +196,8 @@ class LlamaRunner {
       TORCH_CHECK(given == 0 || given == 4,
                   "LlamaRunner: the weight scales qkv_s, o_s, gate_up_s and down_s are given together or not at all");
       w8_ = given == 4;
+      TORCH_CHECK(!(moe_ && (w8_ || activations_fp8)),
+                  "LlamaRunner: a mixture-of-experts model with fp8 or int4 weights or fp8 activations is not supported");
       const std::vector<at::Tensor>* wl[4] = {&qkv_w_, &o_w_, &gate_up_w_, &down_w_};
       const char* names[4] = {"qkv_w", "o_w", "gate_up_w", "down_w"};
       // int4 group-quantised projection weights (W4A16, gemm_w4.hip): the four lists of uint8
@@ -245,6 +284,8 @@ class LlamaRunner {
                         " holds float8_e4m3fn codes but no weight scales were given");
       }
     }
+    TORCH_CHECK(!(moe_ && !process_group.is_none()),
+                "LlamaRunner: a mixture-of-experts model under tensor parallelism is not supported");
     if (!process_group.is_none()) pg_ = py::cast<c10::intrusive_ptr<::c10d::ProcessGroup>>(process_group);
     // LS_ONESHOT_AR=1: decode-sized all-reduces (<= LS_ONESHOT_AR_MAX elements, default
     // 256 x 8192) through the one-shot IPC kernel (allreduce.hip) instead of RCCL.  Both
@@ -264,16 +305,19 @@ class LlamaRunner {
       for (size_t l = 0; l < L; ++l) {
         const at::Tensor* ws[3] = {&qkv_w_[l], &o_w_[l], &down_w_[l]};
         for (auto* w : ws)
-          if (decode_gemm_supported(*w, false))
-            wsz = std::max(wsz, decode_gemm_workspace(kDgemmMaxM, w->size(0), w->size(1), false));
-        if (decode_gemm_supported(gate_up_w_[l], true)) {
+          if (!(moe_ && w == &down_w_[l]) && decode_gemm_supported(*w, false))
+            // at least one f32 slab: the residual + RMSNorm reduction of row_proj reads one even
+            // where K is too short to split (a dense model's gate_up exchange is larger than that)
+            wsz = std::max({wsz, decode_gemm_workspace(kDgemmMaxM, w->size(0), w->size(1), false),
+                            kDgemmMaxM * w->size(0) * 4});
+        if (!moe_ && decode_gemm_supported(gate_up_w_[l], true)) {
           wsz = std::max(wsz, decode_gemm_workspace(kDgemmMaxM, gate_up_w_[l].size(0), gate_up_w_[l].size(1), true));
           fmax = std::max(fmax, gate_up_w_[l].size(0) / 2);
         }
       }
       // the norm-deferred layer (forward_dgemm): combine-path splits must exist for qkv /
       // o / down, the head dim must be 128 (one head per 128-column tile)
-      bool fz = !pg_ && !f8_ && !bias_ && !qknorm_ && head_dim == 128 && fused_env();
+      bool fz = !pg_ && !f8_ && !bias_ && !qknorm_ && !moe_ && head_dim == 128 && fused_env();
       const int64_t H = embed_.size(1);
       for (size_t l = 0; l < L && fz; ++l) {
         const at::Tensor* ws[3] = {&qkv_w_[l], &o_w_[l], &down_w_[l]};
@@ -508,7 +552,7 @@ class LlamaRunner {
     // a qkv bias: gemv_qkv and the RoPE-in-attention kernel do not add one, so the plain
     // GEMV followed by rope_and_cache with the bias; a q / k norm likewise: a head spans
     // several blocks of gemv_qkv)
-    bool fused = gv && !pg_ && !f8_ && !bias_ && !qknorm_ && !w8_;
+    bool fused = gv && !pg_ && !f8_ && !bias_ && !qknorm_ && !w8_ && !moe_;
     for (int64_t l = 0; l < L && fused; ++l)
       fused = gemv_supported(qkv_w_[l], false) && gemv_supported(o_w_[l], false) &&
               gemv_supported(gate_up_w_[l], true) && gemv_supported(down_w_[l], false);
@@ -588,6 +632,20 @@ class LlamaRunner {
       }
       at::Tensor attn = attend(l, qkv, roped);
       at::Tensor o = row_proj(attn, o_w_[l], residual, post_norm_[l], gv, 0, 192);
+      const at::Tensor& nxt = l + 1 < L ? in_norm_[l + 1] : final_norm_;
+      if (moe_) {
+        // mixture of experts (moe.hip): route, grouped gate_up + SwiGLU, grouped down, combine;
+        // every intermediate is sized from T alone, so decode steps still replay as graphs
+        at::Tensor tid = at::empty({T, moe_k_}, o.options().dtype(at::kInt));
+        at::Tensor tw = at::empty({T, moe_k_}, o.options().dtype(at::kFloat));
+        moe_route(tid, tw, o, router_w_[l], moe_norm_);
+        at::Tensor dn = at::empty_like(o);
+        moe_experts(dn, o, xgate_up_w_[l], xdown_w_[l], tid, tw, 0);
+        all_reduce(dn);
+        fused_add_rmsnorm(dn, residual, nxt, eps_);
+        x = dn;
+        continue;
+      }
       at::Tensor a;
       if (gv && gemv_supported(gate_up_w_[l], true)) {
         a = at::empty({T, gate_up_w_[l].size(0) / 2}, o.options());
@@ -599,7 +657,6 @@ class LlamaRunner {
       } else {
         a = proj_silu(o, gate_up_w_[l]);
       }
-      const at::Tensor& nxt = l + 1 < L ? in_norm_[l + 1] : final_norm_;
       x = row_proj(a, down_w_[l], residual, nxt, gv, 48, 256);
     }
     at::Tensor lg = logits_tail(x, rows);
@@ -700,7 +757,7 @@ class LlamaRunner {
     return on;
   }
   bool fused_ready(int64_t T) const {
-    return !w8_ && !bias_ && !qknorm_ && cnt_qkv_.defined() && dgemm_enabled() && T >= std::max(dgemm_min_t(), fused_min_t()) &&
+    return !w8_ && !moe_ && !bias_ && !qknorm_ && cnt_qkv_.defined() && dgemm_enabled() && T >= std::max(dgemm_min_t(), fused_min_t()) &&
            T <= kDgemmMaxM;
   }
 
@@ -907,6 +964,10 @@ class LlamaRunner {
   bool w4_ = false;            // the projections are 4-bit codes with f32 scales and zero points [N, K / G]
   at::Tensor w8_ws_;           // split-K workspace of w8_gemm / w8a8_gemm
   bool a8_ = false;            // fp8 activations: T > 4 projections on the W8A8 kernels (gemm_w8a8.hip)
+  std::vector<at::Tensor> router_w_, xgate_up_w_, xdown_w_;   // per-layer router and expert weight stacks, empty without
+  bool moe_ = false;           // every layer's MLP is a mixture of experts (moe.hip)
+  int64_t moe_k_ = 0;          // experts per token
+  bool moe_norm_ = false;      // the k routing weights are renormalised to sum 1
   c10::optional<at::Tensor> q_norm(int64_t l) const {
     return qknorm_ ? c10::optional<at::Tensor>(q_norm_[l]) : c10::nullopt;
   }
@@ -1540,7 +1601,9 @@ void bind_runners(py::module_& m) {
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>, bool,
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
-                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>>(),
+                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
+                    c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
+                    c10::optional<std::vector<at::Tensor>>, int64_t, bool>(),
            py::arg("embed"), py::arg("qkv_w"), py::arg("o_w"), py::arg("gate_up_w"), py::arg("down_w"),
            py::arg("in_norm"), py::arg("post_norm"), py::arg("final_norm"), py::arg("lm_head"), py::arg("k_caches"),
            py::arg("v_caches"), py::arg("cos_sin"), py::arg("hq"), py::arg("hkv"), py::arg("head_dim"),
@@ -1550,7 +1613,9 @@ void bind_runners(py::module_& m) {
            py::arg("q_norm") = py::none(), py::arg("k_norm") = py::none(), py::arg("qkv_s") = py::none(),
            py::arg("o_s") = py::none(), py::arg("gate_up_s") = py::none(), py::arg("down_s") = py::none(),
            py::arg("activations_fp8") = false, py::arg("qkv_z") = py::none(), py::arg("o_z") = py::none(),
-           py::arg("gate_up_z") = py::none(), py::arg("down_z") = py::none())
+           py::arg("gate_up_z") = py::none(), py::arg("down_z") = py::none(), py::arg("router_w") = py::none(),
+           py::arg("experts_gate_up_w") = py::none(), py::arg("experts_down_w") = py::none(),
+           py::arg("experts_per_token") = 0, py::arg("norm_topk") = false)
       .def("forward", &LlamaRunner::forward, py::call_guard<py::gil_scoped_release>());
   py::class_<BertRunner>(m, "BertRunner")
       .def(py::init<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<std::vector<at::Tensor>>,

@@ -199,6 +199,47 @@ def silu_and_mul(x):
     return (torch.nn.functional.silu(g) * u).to(x.dtype)
 
 
+# ---------------------------------------------------------------- mixture of experts
+# The oracle of ops/csrc/moe.hip, in float64.  router_w [E, H], gate_up_w [E, 2F, H] (an
+# expert's F gate rows, then its F up rows), down_w [E, H, F].  Three roundings to x's dtype
+# define the result: act, each slot's weighted output y[t, s], and the sum over the slots.
+def moe_supported(H: int, F: int, E: int, k: int) -> bool:
+    """The shape rule of the MoE kernels (the same on the CPU, so a model is refused alike)."""
+    return H >= 64 and H % 64 == 0 and F >= 64 and F % 64 == 0 and 1 <= E <= 256 and 1 <= k <= min(E, 16)
+
+
+def moe_route(x, router_w, k: int, norm_topk: bool):
+    """(topk_ids int32 [T, k], topk_w f32 [T, k]) in descending order of weight: softmax over
+    all E experts, the k largest (the lower index on a tie), divided by their sum with
+    ``norm_topk``."""
+    p = torch.softmax(x.double() @ router_w.double().t(), dim=-1)
+    w, ids = torch.sort(p, dim=-1, descending=True, stable=True)
+    w, ids = w[:, :k], ids[:, :k]
+    if norm_topk:
+        w = w / w.sum(-1, keepdim=True)
+    return ids.to(torch.int32).contiguous(), w.to(torch.float32).contiguous()
+
+
+def moe_mlp(x, router_w, gate_up_w, down_w, k: int, norm_topk: bool, route=None, slots: bool = False):
+    """out [T, H] in x's dtype; ``route`` = (topk_ids, topk_w) replaces the router.  With
+    ``slots`` also the per-slot outputs y [T, k, H] (float64 values of x's dtype)."""
+    ids, w = route if route is not None else moe_route(x, router_w, k, norm_topk)
+    T, H = x.shape
+    F = down_w.shape[2]
+    xd = x.double()
+    y = torch.zeros(T, ids.shape[1], H, dtype=torch.float64, device=x.device)
+    for e in ids.unique().tolist():
+        t, s = (ids == e).nonzero(as_tuple=True)
+        gu = xd[t] @ gate_up_w[e].double().t()
+        act = (torch.nn.functional.silu(gu[:, :F]) * gu[:, F:]).to(x.dtype).double()
+        y[t, s] = (w[t, s].double()[:, None] * (act @ down_w[e].double().t())).to(x.dtype).double()
+    out = y[:, 0].clone()
+    for s in range(1, ids.shape[1]):   # slot order
+        out += y[:, s]
+    out = out.to(x.dtype)
+    return (out, y) if slots else out
+
+
 def bias_gelu(x, bias):
     v = x.float() + (bias.float() if bias is not None else 0.0)
     return torch.nn.functional.gelu(v).to(x.dtype)

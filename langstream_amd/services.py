@@ -152,7 +152,7 @@ class ServiceRegistry:
                 if sw is None or sw == "":
                     sw = os.environ.get("LS_SLIDING_WINDOW") or "false"
                 mcfg = llama_config_from_hf(model_path, sliding_window=str(sw).lower() in ("1", "true", "yes"))
-                template = template or ("chatml" if hf_model_type(model_path) in ("qwen2", "qwen3")
+                template = template or ("chatml" if hf_model_type(model_path) in ("qwen2", "qwen3", "qwen3_moe")
                                         else "llama3")
             else:
                 mcfg = PRESETS[name]
