@@ -248,6 +248,7 @@ class LLMEngine:
                       "host_ms": 0.0, "wait_ms": 0.0, "launch_ms": 0.0, "retire_ms": 0.0, "prefix_hit_tokens": 0,
                       "prompt_tokens": 0, "kv_cache_dtype": self.kv_cache_dtype,
                       "weights_dtype": getattr(model, "weights_dtype", "bf16"),
+                      "experts_dtype": getattr(model, "experts_dtype", "bf16"),
                       "activations_dtype": getattr(model, "activations_dtype", "bf16"),
                       "weight_bytes": int(getattr(model, "weight_bytes", 0)),
                       "kv_bytes_per_block": self.kv_bytes_per_block,

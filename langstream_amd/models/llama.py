@@ -239,6 +239,15 @@ WEIGHTS_DTYPES = ("bf16", "fp8", "int4")
 INT4_GROUP = ref.INT4_GROUP   # input columns per scale / zero point when a wider weight is quantised here
 ACTIVATIONS_DTYPES = ("bf16", "fp8")
 W8_NAMES = ("qkv", "o", "gate_up", "down")   # the projections an fp8 / int4 model stores as codes + scales
+EXPERTS_DTYPES = ("bf16", "fp8")
+EXPERT_NAMES = ("experts_gate_up", "experts_down")   # the stacked expert matrices experts_dtype="fp8" stores as codes + scales
+
+
+def quantize_experts_fp8(w: torch.Tensor):
+    """(codes [E, N, K], s f32 [E, N]) of a stacked expert weight: ops.reference.quantize_weight_fp8
+    over its E N rows, one scale per (expert, output row)."""
+    codes, s = ref.quantize_weight_fp8(w.reshape(-1, w.shape[-1]))
+    return codes.view(w.shape), s.view(w.shape[:2])
 
 
 def int4_group(name: str, N: int, K: int, group: int = INT4_GROUP) -> int:
@@ -264,7 +273,7 @@ def tp_kv_heads(num_kv_heads: int, world: int) -> int:
 
 class LlamaLayer:
     def __init__(self, cfg: LlamaConfig, tp: TPInfo, device, dtype, fp8: bool = False, int4: bool = False,
-                 name: str = "layers.?"):
+                 name: str = "layers.?", experts_fp8: bool = False):
         H, D = cfg.hidden_size, cfg.head_dim
         assert cfg.num_heads % tp.world == 0, "TP must divide the query heads"
         assert cfg.intermediate_size % tp.world == 0
@@ -279,11 +288,18 @@ class LlamaLayer:
         # of gate_up_w / down_w: gate_up [E, 2F, H] (an expert's gate rows, then its up rows)
         self.moe = cfg.num_experts > 0
         self.gate_up_w = self.down_w = self.router_w = self.experts_gate_up_w = self.experts_down_w = None
+        self.experts_gate_up_s = self.experts_down_s = None
         if self.moe:
             E, Fm = cfg.num_experts, cfg.moe_intermediate_size
             self.router_w = mk(E, H)
             self.experts_gate_up_w = mk(E, 2 * Fm, H)
             self.experts_down_w = mk(E, H, Fm) / math.sqrt(2 * cfg.num_layers)
+            # fp8 experts: codes + one f32 scale per (expert, output row), quantised here, layer by layer
+            if experts_fp8:
+                for n in EXPERT_NAMES:
+                    codes, sc = quantize_experts_fp8(getattr(self, n + "_w"))
+                    setattr(self, n + "_w", codes)
+                    setattr(self, n + "_s", sc)
         else:
             self.gate_up_w = mk(2 * self.f, H)
             self.down_w = mk(H, self.f) / math.sqrt(2 * cfg.num_layers)
@@ -316,6 +332,8 @@ class LlamaLayer:
     def tensors(self):
         mlp = [self.router_w, self.experts_gate_up_w, self.experts_down_w] if self.moe else [self.gate_up_w, self.down_w]
         t = [self.qkv_w, self.o_w, *mlp, self.in_norm, self.post_norm]
+        if self.experts_gate_up_s is not None:
+            t += [self.experts_gate_up_s, self.experts_down_s]
         if self.qkv_s is not None:
             t += [self.qkv_s, self.o_s, self.gate_up_s, self.down_s]
         if self.qkv_z is not None:
@@ -331,16 +349,23 @@ class LlamaModel:
     """Random-init (or state-dict-loaded) Llama weights + forward over the paged KV cache."""
 
     def __init__(self, cfg: LlamaConfig, device="cuda", dtype=torch.bfloat16, tp: Optional[TPInfo] = None,
-                 seed: int = 0, weights_dtype: str = "bf16", activations_dtype: str = "bf16"):
+                 seed: int = 0, weights_dtype: str = "bf16", activations_dtype: str = "bf16",
+                 experts_dtype: str = "bf16"):
         if weights_dtype not in WEIGHTS_DTYPES:
             raise ValueError(f"weights_dtype must be one of {WEIGHTS_DTYPES}, got {weights_dtype!r}")
         if activations_dtype not in ACTIVATIONS_DTYPES:
             raise ValueError(f"activations_dtype must be one of {ACTIVATIONS_DTYPES}, got {activations_dtype!r}")
+        if experts_dtype not in EXPERTS_DTYPES:
+            raise ValueError(f"experts_dtype must be one of {EXPERTS_DTYPES}, got {experts_dtype!r}")
+        if experts_dtype == "fp8" and not cfg.num_experts:
+            raise ValueError(f"experts_dtype='fp8' on a dense model ({cfg.name}): it has no experts; "
+                             f"weights_dtype='fp8' quantises its projections")
         if cfg.num_experts:
             # refused by name, never silently served
             if weights_dtype != "bf16" or activations_dtype != "bf16":
                 raise ValueError(f"a mixture-of-experts model ({cfg.name}) with fp8 or int4 weights or fp8 activations "
-                                 f"is not supported: quantised experts have no kernel yet")
+                                 f"is not supported, with or without experts_dtype='fp8': only the expert matrices "
+                                 f"have a quantised form (experts_dtype), the other projections stay bf16")
             if tp is not None and tp.world > 1:
                 raise ValueError(f"a mixture-of-experts model ({cfg.name}) under tensor parallelism (world "
                                  f"{tp.world}) is not supported: the experts are not sharded yet")
@@ -360,6 +385,10 @@ class LlamaModel:
         # "int4": they are packed 4-bit codes with an f32 scale and a zero point per group of
         # input columns (W4A16, ops/csrc/gemm_w4.hip; the AWQ / GPTQ family)
         self.weights_dtype = weights_dtype
+        # "fp8": the two stacked expert matrices of every mixture-of-experts layer are float8_e4m3fn
+        # codes with one f32 scale per (expert, output row) and the grouped GEMMs run W8A16
+        # (ops/csrc/moe.hip); the router and every other tensor keep their type and their route
+        self.experts_dtype = experts_dtype
         self.cfg = cfg
         self.device = torch.device(device)
         self.dtype = dtype
@@ -373,7 +402,8 @@ class LlamaModel:
             self.vocab_start = self.tp.rank * self.vocab_per_rank
             self.embed = (torch.randn(self.vocab_per_rank, H, device=self.device) * 0.02).to(dtype)
             self.layers = [LlamaLayer(cfg, self.tp, self.device, dtype, fp8=weights_dtype == "fp8",
-                                      int4=weights_dtype == "int4", name=f"layers.{i}")
+                                      int4=weights_dtype == "int4", name=f"layers.{i}",
+                                      experts_fp8=experts_dtype == "fp8")
                            for i in range(cfg.num_layers)]
             self.final_norm = torch.ones(H, device=self.device, dtype=dtype)
             self.lm_head = self.embed if cfg.tie_embeddings else (
@@ -411,6 +441,8 @@ class LlamaModel:
             names += ("qkv_b",)
         if self.cfg.qk_norm:
             names += ("q_norm", "k_norm")
+        if self.experts_dtype == "fp8":
+            names += tuple(n + "_s" for n in EXPERT_NAMES)
         if self.weights_dtype in ("fp8", "int4"):
             names += tuple(n + "_s" for n in W8_NAMES)
         if self.weights_dtype == "int4":
@@ -437,6 +469,10 @@ class LlamaModel:
                 key = f"layers.{i}.{n}"
                 if (fp8 or int4) and n.endswith(("_s", "_z")):
                     continue   # loaded with its weight below
+                if n[:-2] in EXPERT_NAMES:
+                    if n.endswith("_w"):
+                        self._load_experts(l, n[:-2], key, sd)
+                    continue   # a scale: loaded with its weight
                 src = sd[key]
                 if n.endswith("_w") and n[:-2] in W8_NAMES:
                     zkey = f"layers.{i}.{n[:-2]}_z"
@@ -466,6 +502,32 @@ class LlamaModel:
                         getattr(l, n[:-2] + "_s").copy_(sc)
                         continue
                 getattr(l, n).copy_(src)
+
+    def _load_experts(self, layer: LlamaLayer, n: str, key: str, sd: dict) -> None:
+        """One stacked expert matrix: as it is for bf16 experts; for fp8 experts the (codes, scale)
+        pair of the state dict, or a wider tensor quantised here with the one rule."""
+        src, skey, dst = sd[key], key[:-2] + "_s", getattr(layer, n + "_w")
+        if self.experts_dtype != "fp8":
+            if ref.is_fp8(src) or skey in sd:
+                raise ValueError(f"{key} holds float8_e4m3fn codes but the model's experts_dtype is 'bf16'; build "
+                                 f"the model with experts_dtype='fp8'")
+            dst.copy_(src)
+            return
+        if ref.is_fp8(src):
+            if skey not in sd:
+                raise ValueError(f"{key} holds float8_e4m3fn codes but {skey} is missing")
+            codes, sc = src, sd[skey].to(torch.float32)
+            if tuple(sc.shape) != tuple(dst.shape[:2]):
+                raise ValueError(f"{skey} has shape {tuple(sc.shape)}, expected one scale per (expert, row) "
+                                 f"{tuple(dst.shape[:2])}")
+        elif skey in sd:
+            raise ValueError(f"{skey} is present but {key} holds {src.dtype}, not float8_e4m3fn codes")
+        else:   # a wider tensor: quantise it with the one rule
+            codes, sc = quantize_experts_fp8(src.to(self.device))
+        if tuple(codes.shape) != tuple(dst.shape):
+            raise ValueError(f"{key} has shape {tuple(codes.shape)}, expected {tuple(dst.shape)}")
+        dst.view(torch.uint8).copy_(codes.contiguous().view(torch.uint8))
+        getattr(layer, n + "_s").copy_(sc)
 
     def _load_int4(self, layer: LlamaLayer, n: str, key: str, sd: dict) -> None:
         """One projection of an int4 model: the (codes, scale, zero) triple of the state dict
@@ -541,7 +603,8 @@ class LlamaModel:
             ops.fused_add_rmsnorm(o, residual, layer.post_norm, eps)
             if layer.moe:
                 d = ops.moe_mlp(o, layer.router_w, layer.experts_gate_up_w, layer.experts_down_w,
-                                cfg.experts_per_token, cfg.norm_topk_prob)
+                                cfg.experts_per_token, cfg.norm_topk_prob, gate_up_s=layer.experts_gate_up_s,
+                                down_s=layer.experts_down_s)
                 a = None
             elif layer.gate_up_s is not None:
                 gu = _linear(o, layer.gate_up_w, layer.gate_up_s, a8, layer.gate_up_z)
@@ -590,7 +653,8 @@ class LlamaModel:
             **({n + "_z": [getattr(l, n + "_z") for l in L] for n in W8_NAMES} if self.weights_dtype == "int4" else {}),
             **(dict(router_w=[l.router_w for l in L], experts_gate_up_w=[l.experts_gate_up_w for l in L],
                     experts_down_w=[l.experts_down_w for l in L], experts_per_token=self.cfg.experts_per_token,
-                    norm_topk=self.cfg.norm_topk_prob) if moe else {}))
+                    norm_topk=self.cfg.norm_topk_prob) if moe else {}),
+            **({n + "_s": [getattr(l, n + "_s") for l in L] for n in EXPERT_NAMES} if self.experts_dtype == "fp8" else {}))
         self._runner = (key, runner, kv_caches)
         return runner
 

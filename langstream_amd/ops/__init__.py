@@ -279,19 +279,32 @@ def moe_route(x, router_w, k: int, norm_topk: bool):
     return ref.moe_route(x, router_w, k, norm_topk)
 
 
-def moe_mlp(x, router_w, gate_up_w, down_w, k: int, norm_topk: bool, out=None, route=None, tile_rows: int = 0):
+def moe_mlp(x, router_w, gate_up_w, down_w, k: int, norm_topk: bool, out=None, route=None, tile_rows: int = 0,
+            gate_up_s=None, down_s=None):
     """Sparse MoE MLP: out[t] = sum over the k routed experts e of topk_w * down_w[e] .
     (silu(gate_w[e] . x_t) * (up_w[e] . x_t)), with gate_up_w [E, 2F, H] and down_w [E, H, F]
     (ops/csrc/moe.hip: route, align, two grouped GEMMs, combine; rounding points in
     ops.reference.moe_mlp).  ``route`` = (topk_ids, topk_w) replaces the router;
-    ``tile_rows`` 32 or 128 forces the row-tile height of the grouped GEMMs (0: the rule)."""
+    ``tile_rows`` 32 or 128 forces the row-tile height of the grouped GEMMs (0: the rule).
+    With ``gate_up_s`` f32 [E, 2F] and ``down_s`` f32 [E, H] the expert weights are
+    float8_e4m3fn codes with one scale per (expert, output row) and the grouped GEMMs run
+    W8A16: the scale multiplies the f32 sum once."""
     _moe_check(x, router_w, k, down_w.shape[2])
+    if (gate_up_s is None) != (down_s is None):
+        raise ValueError("moe_mlp: gate_up_s and down_s are given together or not at all")
+    if gate_up_s is None and (ref.is_fp8(gate_up_w) or ref.is_fp8(down_w)):
+        raise ValueError("moe_mlp: the expert weights hold float8_e4m3fn codes but gate_up_s / down_s were not given")
     if _gpu(x, gate_up_w, down_w):
         ids, w = route if route is not None else moe_route(x, router_w, k, norm_topk)
         out = torch.empty_like(x) if out is None else out
-        hip().moe_experts(out, x, gate_up_w, down_w, ids, w, tile_rows)
+        hip().moe_experts(out, x, gate_up_w, down_w, ids, w, tile_rows, gate_up_s, down_s)
         return out
-    r = ref.moe_mlp(x, router_w, gate_up_w, down_w, k, norm_topk, route=route)
+    if gate_up_s is not None:
+        E, F2, H = gate_up_w.shape
+        for name, s, shape in (("gate_up_s", gate_up_s, (E, F2)), ("down_s", down_s, (E, H))):
+            if s.dtype != torch.float32 or tuple(s.shape) != shape:
+                raise ValueError(f"moe_mlp: {name} must be float32 {shape}, got {s.dtype} {tuple(s.shape)}")
+    r = ref.moe_mlp(x, router_w, gate_up_w, down_w, k, norm_topk, route=route, gate_up_s=gate_up_s, down_s=down_s)
     if out is not None:
         out.copy_(r)
         return out
@@ -301,7 +314,7 @@ def moe_mlp(x, router_w, gate_up_w, down_w, k: int, norm_topk: bool, out=None, r
 def moe_launch_counts(reset: bool = False) -> dict:
     """Launches of the MoE kernels since the last reset: "route_mfma" / "route_dot",
     "align", "gate_up_bm32" / "gate_up_bm128", "down_bm32" / "down_bm128" (the row-tile
-    height of the grouped GEMMs), "combine"."""
+    height of the grouped GEMMs; "gate_up_w8_bm32" ... "down_w8_bm128" with fp8 experts), "combine"."""
     return dict(hip().moe_launch_counts(reset))
 
 

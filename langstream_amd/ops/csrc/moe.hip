@@ -36,6 +36,19 @@
 //   BM = 32 (waves side by side along the columns; weights on non-temporal loads, each byte
 //   is used once) serves decode, BM = 128 (waves stacked along the rows) prefill; tile_rows()
 //   is the rule.
+// moe_gemm_w8 the same grouped GEMM over fp8 (e4m3fn) expert weights with one f32 scale per (expert,
+//   weight row), W8A16: y = (a . code^T) * s.  A code decodes to bf16 exactly, so the products run
+//   on the bf16 MFMA; the weights cross HBM, L2 and LDS as bytes and are expanded at the MFMA
+//   operand (fp8_unpack8).  The scale multiplies the f32 accumulator once, in the epilogue: the
+//   gate and the up scale before SwiGLU, the down scale before topk_w and the one rounding.
+//   K STEP: BM = 32 steps K by 128 codes, BM = 128 by 64.  The 32-row form lives on the bytes
+//   it keeps in flight; with a 64-code step a thread would issue half the 16-B weight loads per
+//   step that the bf16 kernel does (a row of 64 codes is four chunks, not eight), so its step is
+//   doubled to keep the same four (gate_up) or two (down) loads per thread in flight.  A K that
+//   is an odd multiple of 64 ends in a half step whose upper chunks are zeros.  Measured at
+//   T = 16 (profiles/moe_fp8/README.md): 143 us against 186 us with a 64-code step on the
+//   Qwen3-30B-A3B shape, 347 against 510 us on the Mixtral shape.  BM = 128 is compute-bound and
+//   keeps 64: two stages of its A tile and a 128-code weight tile would not fit in 64 KB.
 // moe_combine out[t] = bf16(sum_s y[t, s]) with 16-B loads.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -353,6 +366,167 @@ __global__ void __launch_bounds__(256) moe_gemm_kernel(const bf16* __restrict__ 
     }
 }
 
+// ---------------------------------------------------------------------------- moe_gemm_w8
+// The grouped GEMM over fp8 expert weights (W8A16): w holds e4m3fn codes, one byte each, sc one
+// f32 scale per (expert, weight row) -- [E, 2 N] in gate_up mode, [E, N] in down mode.  Schedule,
+// gather, scatter, tile heights and grid are those of moe_gemm_kernel; A stays bf16 in LDS.  The
+// weight tile stays codes from HBM to LDS (rows of BKW + 16 bytes) and a lane expands the 8 codes
+// of an MFMA operand from one 8-B LDS read (fp8_unpack8, exact).  The scales touch only the f32
+// accumulators in the epilogue and are loaded ahead of the K loop.  A K that is an odd multiple
+// of 64 ends the 128-code form in a half step: its upper chunks are zeros and read nothing.
+template <int BM, bool DOWN>
+__global__ void __launch_bounds__(256) moe_gemm_w8_kernel(const bf16* __restrict__ a, int64_t lda,
+                                                          const fp8_t* __restrict__ w, const float* __restrict__ sc,
+                                                          const int* __restrict__ num_tiles,
+                                                          const int* __restrict__ tile_expert,
+                                                          const int* __restrict__ sorted_rows,
+                                                          const float* __restrict__ topk_w, int kk, int K, int N,
+                                                          bf16* __restrict__ out) {
+  constexpr int BKW = BM == 32 ? 128 : 64;          // K step in codes (file header: K STEP)
+  constexpr int NW = DOWN ? BN : 2 * BN;            // weight rows per K step
+  constexpr int LDA = BKW + 8;                      // A LDS row, bf16 elements
+  constexpr int LDW = BKW + 16;                     // W LDS row, bytes (80 / 144: 16-B stores and 8-B reads stay aligned)
+  constexpr int AS = BM * LDA * 2, WS = NW * LDW, STAGE = AS + WS;
+  constexpr int ACR = BKW / 8, WCR = BKW / 16;      // 16-B chunks per A row (8 bf16) and per W row (16 codes)
+  constexpr int AC = BM * ACR / 256, WC = NW * WCR / 256;   // chunks per thread per K step
+  constexpr int WAVES_M = BM == 128 ? 4 : 1, WAVES_N = 4 / WAVES_M;
+  constexpr int IT = BM / WAVES_M / 16, JT = BN / WAVES_N / 16;
+  static_assert(BM == 32 || BM == 128, "tile heights");
+  static_assert(2 * STAGE <= 65536 - 4 * BM, "two LDS stages");
+  __shared__ __attribute__((aligned(16))) char lds[2 * STAGE];
+  __shared__ int srow[BM];
+  const int tile = blockIdx.y;
+  if (tile >= *num_tiles) return;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int e = tile_expert[tile];
+  const int n0 = blockIdx.x * BN;
+  const int64_t prow0 = (int64_t)tile * BM;
+  if (tid < BM) srow[tid] = sorted_rows[prow0 + tid];
+  __syncthreads();
+
+  const bf16* ap[AC];
+  bool aok[AC];
+#pragma unroll
+  for (int i = 0; i < AC; ++i) {
+    const int q = tid + 256 * i, row = q / ACR, c = q % ACR;
+    const int idx = srow[row];
+    aok[i] = idx >= 0;
+    const int64_t grow = DOWN ? prow0 + row : (aok[i] ? idx / kk : 0);
+    ap[i] = a + grow * lda + c * 8;
+  }
+  const fp8_t* wp[WC];
+  const fp8_t* wbase = w + (int64_t)e * (DOWN ? N : 2 * N) * K;
+#pragma unroll
+  for (int i = 0; i < WC; ++i) {
+    const int q = tid + 256 * i, row = q / WCR, c = q % WCR;
+    const int grow = DOWN || row < BN ? n0 + row : N + n0 + row - BN;   // gate rows, then the matching up rows
+    wp[i] = wbase + (int64_t)grow * K + c * 16;
+  }
+  uint4 ra[AC], rw[WC];
+  auto gload = [&](int kt) {
+    const int ko = kt * BKW;
+#pragma unroll
+    for (int i = 0; i < AC; ++i) {
+      const bool in = BKW == 64 || ko + ((tid + 256 * i) % ACR) * 8 < K;   // false past K in a half step
+      ra[i] = aok[i] && in ? ld16(ap[i] + ko) : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < WC; ++i) {
+      const bool in = BKW == 64 || ko + ((tid + 256 * i) % WCR) * 16 < K;
+      rw[i] = !in ? make_uint4(0, 0, 0, 0) : BM == 32 ? ld16_nt(wp[i] + ko) : ld16(wp[i] + ko);
+    }
+  };
+  auto lstore = [&](int buf) {
+    char* la = lds + buf * STAGE;
+    char* lw = la + AS;
+#pragma unroll
+    for (int i = 0; i < AC; ++i) {
+      const int q = tid + 256 * i;
+      st16(la + ((q / ACR) * LDA + (q % ACR) * 8) * 2, ra[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < WC; ++i) {
+      const int q = tid + 256 * i;
+      st16(lw + (q / WCR) * LDW + (q % WCR) * 16, rw[i]);
+    }
+  };
+
+  const int rb = (BM == 128 ? wid : 0) * (BM / WAVES_M);    // first tile row of this wave
+  const int cb = (BM == 128 ? 0 : wid) * (BN / WAVES_N);    // first tile column of this wave
+  const int fr = lane & 15, fk = 8 * (lane >> 4);
+  // this lane's output columns are n0 + cb + 16 j + fr: their scales, once per tile
+  float sg[JT], su[DOWN ? 1 : JT];
+  const float* se = sc + (int64_t)e * (DOWN ? N : 2 * N) + n0 + cb + fr;
+#pragma unroll
+  for (int j = 0; j < JT; ++j) {
+    sg[j] = se[16 * j];
+    if constexpr (!DOWN) su[j] = se[N + 16 * j];
+  }
+  f32x4 accg[IT][JT], accu[DOWN ? 1 : IT][DOWN ? 1 : JT];
+#pragma unroll
+  for (int i = 0; i < IT; ++i)
+#pragma unroll
+    for (int j = 0; j < JT; ++j) {
+      accg[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (!DOWN) accu[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+
+  const int nk = (K + BKW - 1) / BKW;
+  gload(0);
+  lstore(0);
+  if (nk > 1) gload(1);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const char* la = lds + (kt & 1) * STAGE;
+    const char* lw = la + AS;
+#pragma unroll
+    for (int ks = 0; ks < BKW / 32; ++ks) {
+      bf16x8 av[IT];
+#pragma unroll
+      for (int i = 0; i < IT; ++i) av[i] = lds8(la + ((rb + 16 * i + fr) * LDA + 32 * ks + fk) * 2);
+#pragma unroll
+      for (int j = 0; j < JT; ++j) {
+        const bf16x8 bg = fp8_unpack8(*reinterpret_cast<const uint2*>(lw + (cb + 16 * j + fr) * LDW + 32 * ks + fk));
+#pragma unroll
+        for (int i = 0; i < IT; ++i) accg[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i], bg, accg[i][j], 0, 0, 0);
+        if constexpr (!DOWN) {
+          const bf16x8 bu =
+              fp8_unpack8(*reinterpret_cast<const uint2*>(lw + (BN + cb + 16 * j + fr) * LDW + 32 * ks + fk));
+#pragma unroll
+          for (int i = 0; i < IT; ++i)
+            accu[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i], bu, accu[i][j], 0, 0, 0);
+        }
+      }
+    }
+    if (kt + 1 < nk) {
+      lstore((kt + 1) & 1);
+      if (kt + 2 < nk) gload(kt + 2);
+    }
+    __syncthreads();
+  }
+
+  // acc[i][j][r] = C[rb + 16 i + 4 (lane >> 4) + r][cb + 16 j + fr] (tile-local), still unscaled
+#pragma unroll
+  for (int i = 0; i < IT; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = rb + 16 * i + 4 * (lane >> 4) + r;
+      const int idx = srow[row];
+      if (idx < 0) continue;   // padding row
+      const float tw = DOWN ? topk_w[idx] : 0.f;
+      bf16* orow = out + (DOWN ? (int64_t)idx : prow0 + row) * N + n0 + cb + fr;
+#pragma unroll
+      for (int j = 0; j < JT; ++j) {
+        if constexpr (DOWN) {
+          orow[16 * j] = (bf16)(tw * (accg[i][j][r] * sg[j]));
+        } else {
+          const float g = accg[i][j][r] * sg[j];
+          orow[16 * j] = (bf16)(g / (1.f + expf(-g)) * (accu[i][j][r] * su[j]));
+        }
+      }
+    }
+}
+
 // ---------------------------------------------------------------------------- moe_combine
 // One thread per 16-B chunk of out.
 __global__ void __launch_bounds__(256) moe_combine_kernel(const bf16* __restrict__ y, const int* __restrict__ ids,
@@ -376,6 +550,7 @@ __global__ void __launch_bounds__(256) moe_combine_kernel(const bf16* __restrict
 
 // Host-side launch census (moe_launch_counts), relaxed atomics on the host only.
 std::atomic<int64_t> g_route[2], g_align, g_gemm[2][2], g_combine;   // route [mfma]; gemm [BM == 128][down]
+std::atomic<int64_t> g_gemm_w8[2][2];                                // the fp8-code GEMMs, likewise
 
 bool aligned16(const at::Tensor& t) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0; }
 
@@ -405,6 +580,24 @@ void gemm_launch(hipStream_t st, const at::Tensor& x, const at::Tensor& gate_up_
       nullptr, k, H, F, act);
   moe_gemm_kernel<BM, true><<<dim3(H / BN, (unsigned)max_tiles), 256, 0, st>>>(
       act, F, (const bf16*)down_w.data_ptr(), meta, tile_expert, sorted_rows, wts, k, F, H, y);
+}
+
+// The same two launches over fp8 codes and their scales.
+template <int BM>
+void gemm_w8_launch(hipStream_t st, const at::Tensor& x, const at::Tensor& gate_up_w, const at::Tensor& down_w,
+                    const at::Tensor& gate_up_s, const at::Tensor& down_s, const int* meta, int64_t max_tiles,
+                    const float* wts, int k, bf16* act, bf16* y) {
+  const int H = (int)x.size(1), F = (int)down_w.size(2);
+  const int* tile_expert = meta + 1;
+  const int* sorted_rows = meta + 1 + max_tiles;
+  g_gemm_w8[BM == 128][0].fetch_add(1, std::memory_order_relaxed);
+  g_gemm_w8[BM == 128][1].fetch_add(1, std::memory_order_relaxed);
+  moe_gemm_w8_kernel<BM, false><<<dim3(F / BN, (unsigned)max_tiles), 256, 0, st>>>(
+      (const bf16*)x.data_ptr(), x.stride(0), (const fp8_t*)gate_up_w.data_ptr(), gate_up_s.data_ptr<float>(), meta,
+      tile_expert, sorted_rows, nullptr, k, H, F, act);
+  moe_gemm_w8_kernel<BM, true><<<dim3(H / BN, (unsigned)max_tiles), 256, 0, st>>>(
+      act, F, (const fp8_t*)down_w.data_ptr(), down_s.data_ptr<float>(), meta, tile_expert, sorted_rows, wts, k, F, H,
+      y);
 }
 
 }  // namespace
@@ -445,17 +638,46 @@ void moe_route(at::Tensor ids, at::Tensor wts, at::Tensor x, at::Tensor router_w
 }
 
 // out[t] = sum over the k slots of row t of topk_w * expert(x_t): moe_align, the two grouped
-// GEMMs and moe_combine.  tile_rows_force: 0 for the rule, else 32 or 128.
+// GEMMs and moe_combine.  tile_rows_force: 0 for the rule, else 32 or 128.  With the scales
+// gate_up_s f32 [E, 2F] and down_s f32 [E, H] (together or not at all) the weights are
+// float8_e4m3fn codes and the W8 kernels run; without them the weights are bf16.
 void moe_experts(at::Tensor out, at::Tensor x, at::Tensor gate_up_w, at::Tensor down_w, at::Tensor ids,
-                 at::Tensor wts, int64_t tile_rows_force) {
-  TORCH_CHECK(gate_up_w.is_cuda() && down_w.is_cuda() && gate_up_w.scalar_type() == at::kBFloat16 &&
-                  down_w.scalar_type() == at::kBFloat16 && gate_up_w.dim() == 3 && down_w.dim() == 3 &&
+                 at::Tensor wts, int64_t tile_rows_force, c10::optional<at::Tensor> gate_up_s,
+                 c10::optional<at::Tensor> down_s) {
+  TORCH_CHECK(gate_up_s.has_value() == down_s.has_value(),
+              "moe_experts: gate_up_s and down_s are given together or not at all");
+  const bool w8 = gate_up_s.has_value();
+  const auto wt = gate_up_w.scalar_type();
+  TORCH_CHECK(w8 || (wt != at::kFloat8_e4m3fn && down_w.scalar_type() != at::kFloat8_e4m3fn),
+              "moe_experts: the expert weights hold float8_e4m3fn codes but no scales (gate_up_s, down_s) were given");
+  TORCH_CHECK(!w8 || (wt == at::kFloat8_e4m3fn && down_w.scalar_type() == at::kFloat8_e4m3fn),
+              "moe_experts: with gate_up_s / down_s the expert weights must be float8_e4m3fn codes, got ", wt, " and ",
+              down_w.scalar_type());
+  TORCH_CHECK(gate_up_w.is_cuda() && down_w.is_cuda() && (w8 || wt == at::kBFloat16) &&
+                  down_w.scalar_type() == wt && gate_up_w.dim() == 3 && down_w.dim() == 3 &&
                   gate_up_w.is_contiguous() && down_w.is_contiguous() && aligned16(gate_up_w) && aligned16(down_w),
-              "moe_experts: gate_up_w [E, 2F, H] and down_w [E, H, F] must be contiguous 16-byte aligned bf16 on the GPU");
+              "moe_experts: gate_up_w [E, 2F, H] and down_w [E, H, F] must be contiguous 16-byte aligned bf16 (with "
+              "scales: float8_e4m3fn) on the GPU");
   const int64_t E = gate_up_w.size(0), H = gate_up_w.size(2), F = down_w.size(2);
   TORCH_CHECK(gate_up_w.size(1) == 2 * F && down_w.size(0) == E && down_w.size(1) == H,
               "moe_experts: gate_up_w ", gate_up_w.sizes(), " and down_w ", down_w.sizes(),
               " are not [E, 2F, H] and [E, H, F]");
+  if (w8) {
+    const at::Tensor* ss[2] = {&*gate_up_s, &*down_s};
+    const char* names[2] = {"gate_up_s", "down_s"};
+    const int64_t rows[2] = {2 * F, H};
+    for (int i = 0; i < 2; ++i) {
+      const at::Tensor& s = *ss[i];
+      TORCH_CHECK(s.is_cuda() && s.device() == gate_up_w.device(), "moe_experts: ", names[i],
+                  " must be on the device of the weights");
+      TORCH_CHECK(s.scalar_type() == at::kFloat, "moe_experts: ", names[i], " must be float32, got ", s.scalar_type());
+      TORCH_CHECK(s.dim() == 2 && s.size(0) == E && s.size(1) == rows[i], "moe_experts: ", names[i], " has shape ",
+                  s.sizes(), ", expected one scale per (expert, row) [", E, ", ", rows[i], "]");
+      TORCH_CHECK(s.is_contiguous(), "moe_experts: ", names[i], " must be contiguous");
+      TORCH_CHECK((reinterpret_cast<uintptr_t>(s.data_ptr()) & 3) == 0, "moe_experts: ", names[i],
+                  " must be 4-byte aligned");
+    }
+  }
   check_x("moe_experts", x, H);
   const int64_t T = x.size(0);
   TORCH_CHECK(ids.dim() == 2 && ids.size(0) == T, "moe_experts: topk_ids must be [T, k]");
@@ -485,7 +707,13 @@ void moe_experts(at::Tensor out, at::Tensor x, at::Tensor gate_up_w, at::Tensor 
   int* mp = meta.data_ptr<int>();
   g_align.fetch_add(1, std::memory_order_relaxed);
   moe_align_kernel<<<1, 1024, 0, st>>>(ids.data_ptr<int>(), (int)n, (int)E, BM, mp, mp + 1, mp + 1 + max_tiles);
-  if (BM == 32)
+  if (w8 && BM == 32)
+    gemm_w8_launch<32>(st, x, gate_up_w, down_w, *gate_up_s, *down_s, mp, max_tiles, wts.data_ptr<float>(), (int)k,
+                       (bf16*)act.data_ptr(), (bf16*)y.data_ptr());
+  else if (w8)
+    gemm_w8_launch<128>(st, x, gate_up_w, down_w, *gate_up_s, *down_s, mp, max_tiles, wts.data_ptr<float>(), (int)k,
+                        (bf16*)act.data_ptr(), (bf16*)y.data_ptr());
+  else if (BM == 32)
     gemm_launch<32>(st, x, gate_up_w, down_w, mp, max_tiles, wts.data_ptr<float>(), (int)k, (bf16*)act.data_ptr(),
                     (bf16*)y.data_ptr());
   else
@@ -499,7 +727,8 @@ void moe_experts(at::Tensor out, at::Tensor x, at::Tensor gate_up_w, at::Tensor 
 }
 
 // The launch census since the last reset: {"route_mfma": n, "route_dot": n, "align": n,
-// "gate_up_bm32": n, "down_bm128": n, "combine": n} (keys with a zero count are left out).
+// "gate_up_bm32": n, "down_bm128": n, "gate_up_w8_bm32": n, "down_w8_bm128": n, "combine": n} (keys
+// with a zero count are left out; the w8 keys count the fp8-code GEMMs).
 pybind11::dict moe_launch_counts(bool reset) {
   pybind11::dict d;
   auto put = [&](const std::string& key, std::atomic<int64_t>& c) {
@@ -512,6 +741,8 @@ pybind11::dict moe_launch_counts(bool reset) {
   for (int b = 0; b < 2; ++b) {
     put(std::string("gate_up_bm") + (b ? "128" : "32"), g_gemm[b][0]);
     put(std::string("down_bm") + (b ? "128" : "32"), g_gemm[b][1]);
+    put(std::string("gate_up_w8_bm") + (b ? "128" : "32"), g_gemm_w8[b][0]);
+    put(std::string("down_w8_bm") + (b ? "128" : "32"), g_gemm_w8[b][1]);
   }
   put("combine", g_combine);
   return d;

@@ -284,11 +284,13 @@ void w4_launch_counts(pybind11::dict& d, bool reset);   // adds its keys to the 
 
 // ---------------------------------------------------------------------------- moe.hip
 // Sparse mixture-of-experts MLP: router_w [E, H], gate_up_w [E, 2F, H], down_w [E, H, F], all bf16;
-// topk_ids int32 / topk_w f32 [T, k].
+// topk_ids int32 / topk_w f32 [T, k].  With gate_up_s f32 [E, 2F] and down_s f32 [E, H] the two expert
+// stacks are float8_e4m3fn codes with one scale per (expert, output row).
 bool moe_supported(int64_t H, int64_t F, int64_t E, int64_t k);
 void moe_route(at::Tensor ids, at::Tensor wts, at::Tensor x, at::Tensor router_w, bool norm_topk);
 void moe_experts(at::Tensor out, at::Tensor x, at::Tensor gate_up_w, at::Tensor down_w, at::Tensor ids,
-                 at::Tensor wts, int64_t tile_rows_force);
+                 at::Tensor wts, int64_t tile_rows_force, c10::optional<at::Tensor> gate_up_s,
+                 c10::optional<at::Tensor> down_s);
 pybind11::dict moe_launch_counts(bool reset);
 
 // -------------------------------------------------------------------------- runner.hip

@@ -111,7 +111,8 @@ class LlamaRunner {
               c10::optional<std::vector<at::Tensor>> router_w = c10::nullopt,
               c10::optional<std::vector<at::Tensor>> experts_gate_up_w = c10::nullopt,
               c10::optional<std::vector<at::Tensor>> experts_down_w = c10::nullopt, int64_t experts_per_token = 0,
-              bool norm_topk = false)
+              bool norm_topk = false, c10::optional<std::vector<at::Tensor>> experts_gate_up_s = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> experts_down_s = c10::nullopt)
       : embed_(embed), qkv_w_(qkv_w), o_w_(o_w), gate_up_w_(gate_up_w), down_w_(down_w), in_norm_(in_norm),
         post_norm_(post_norm), final_norm_(final_norm), lm_head_(lm_head), kc_(k_caches), vc_(v_caches),
         cos_sin_(cos_sin), hq_(hq), hkv_(hkv), d_(head_dim), eps_(eps), scale_(scale), vocab_(vocab_size),
@@ -127,6 +128,15 @@ class LlamaRunner {
       TORCH_CHECK(given == 0 || given == 3,
                   "LlamaRunner: router_w, experts_gate_up_w and experts_down_w are given together or not at all");
       moe_ = given == 3;
+    }
+    // fp8 experts (moe_gemm_w8): the two per-layer lists of f32 scales, one per (expert, output
+    // row), are given together or not at all; given, the expert stacks are float8_e4m3fn codes
+    {
+      const bool gs = experts_gate_up_s.has_value() && !experts_gate_up_s->empty();
+      const bool ds = experts_down_s.has_value() && !experts_down_s->empty();
+      TORCH_CHECK(gs == ds, "LlamaRunner: experts_gate_up_s and experts_down_s are given together or not at all");
+      TORCH_CHECK(!gs || moe_, "LlamaRunner: experts_gate_up_s / experts_down_s without the expert weight lists");
+      xw8_ = gs;
     }
     if (moe_) {
       router_w_ = *router_w;
@@ -146,6 +156,29 @@ class LlamaRunner {
         TORCH_CHECK(moe_supported(r.size(1), d.size(2), r.size(0), moe_k_), "LlamaRunner: layers.", l,
                     " mixture of experts with H = ", r.size(1), ", F = ", d.size(2), ", E = ", r.size(0), ", k = ", moe_k_,
                     " is outside the MoE shape rule (H % 64 == 0, F % 64 == 0, E <= 256, 1 <= k <= min(E, 16))");
+        const bool codes[2] = {g.scalar_type() == at::kFloat8_e4m3fn, d.scalar_type() == at::kFloat8_e4m3fn};
+        const char* wn[2] = {"experts_gate_up", "experts_down"};
+        for (int i = 0; i < 2; ++i)
+          TORCH_CHECK(codes[i] == xw8_, "LlamaRunner: layers.", l, ".", wn[i], "_w ",
+                      xw8_ ? "must be float8_e4m3fn codes with expert scales"
+                           : "holds float8_e4m3fn codes but no expert scales were given");
+      }
+      if (xw8_) {
+        xgate_up_s_ = *experts_gate_up_s;
+        xdown_s_ = *experts_down_s;
+        TORCH_CHECK(xgate_up_s_.size() == L && xdown_s_.size() == L,
+                    "LlamaRunner: one experts_gate_up_s and one experts_down_s per layer");
+        for (size_t l = 0; l < L; ++l) {
+          const at::Tensor* ss[2] = {&xgate_up_s_[l], &xdown_s_[l]};
+          const at::Tensor* ws[2] = {&xgate_up_w_[l], &xdown_w_[l]};
+          const char* sn[2] = {"experts_gate_up_s", "experts_down_s"};
+          for (int i = 0; i < 2; ++i)
+            TORCH_CHECK(ss[i]->is_cuda() && ss[i]->device() == ws[i]->device() && ss[i]->scalar_type() == at::kFloat &&
+                            ss[i]->is_contiguous() && ss[i]->dim() == 2 && ss[i]->size(0) == ws[i]->size(0) &&
+                            ss[i]->size(1) == ws[i]->size(1),
+                        "LlamaRunner: layers.", l, ".", sn[i], " must be a contiguous float32 [", ws[i]->size(0), ", ",
+                        ws[i]->size(1), "] on the device of the weight");
+        }
       }
       gate_up_w_ = xgate_up_w_;   // placeholders so the per-layer lists keep one entry per layer; never a GEMM operand
       down_w_ = xdown_w_;
@@ -278,7 +311,7 @@ class LlamaRunner {
         w8_ws_ = at::empty({std::max<int64_t>(wsz / 4, 4)}, embed_.options().dtype(at::kFloat));
       } else {
         TORCH_CHECK(!activations_fp8, "LlamaRunner: fp8 activations need fp8 weights (the four weight scale lists)");
-        for (int k = 0; k < 4; ++k)
+        for (int k = 0; k < (moe_ ? 2 : 4); ++k)   // the expert stacks were checked against their own scales
           for (size_t l = 0; l < L; ++l)
             TORCH_CHECK((*wl[k])[l].scalar_type() != at::kFloat8_e4m3fn, "LlamaRunner: layers.", l, ".", names[k],
                         " holds float8_e4m3fn codes but no weight scales were given");
@@ -640,7 +673,10 @@ class LlamaRunner {
         at::Tensor tw = at::empty({T, moe_k_}, o.options().dtype(at::kFloat));
         moe_route(tid, tw, o, router_w_[l], moe_norm_);
         at::Tensor dn = at::empty_like(o);
-        moe_experts(dn, o, xgate_up_w_[l], xdown_w_[l], tid, tw, 0);
+        if (xw8_)
+          moe_experts(dn, o, xgate_up_w_[l], xdown_w_[l], tid, tw, 0, xgate_up_s_[l], xdown_s_[l]);
+        else
+          moe_experts(dn, o, xgate_up_w_[l], xdown_w_[l], tid, tw, 0, c10::nullopt, c10::nullopt);
         all_reduce(dn);
         fused_add_rmsnorm(dn, residual, nxt, eps_);
         x = dn;
@@ -965,6 +1001,8 @@ class LlamaRunner {
   at::Tensor w8_ws_;           // split-K workspace of w8_gemm / w8a8_gemm
   bool a8_ = false;            // fp8 activations: T > 4 projections on the W8A8 kernels (gemm_w8a8.hip)
   std::vector<at::Tensor> router_w_, xgate_up_w_, xdown_w_;   // per-layer router and expert weight stacks, empty without
+  std::vector<at::Tensor> xgate_up_s_, xdown_s_;   // fp8 experts: f32 scales [E, 2F] / [E, H] per layer, empty without
+  bool xw8_ = false;           // the expert stacks are float8_e4m3fn codes with those scales
   bool moe_ = false;           // every layer's MLP is a mixture of experts (moe.hip)
   int64_t moe_k_ = 0;          // experts per token
   bool moe_norm_ = false;      // the k routing weights are renormalised to sum 1
@@ -1603,7 +1641,8 @@ void bind_runners(py::module_& m) {
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
-                    c10::optional<std::vector<at::Tensor>>, int64_t, bool>(),
+                    c10::optional<std::vector<at::Tensor>>, int64_t, bool, c10::optional<std::vector<at::Tensor>>,
+                    c10::optional<std::vector<at::Tensor>>>(),
            py::arg("embed"), py::arg("qkv_w"), py::arg("o_w"), py::arg("gate_up_w"), py::arg("down_w"),
            py::arg("in_norm"), py::arg("post_norm"), py::arg("final_norm"), py::arg("lm_head"), py::arg("k_caches"),
            py::arg("v_caches"), py::arg("cos_sin"), py::arg("hq"), py::arg("hkv"), py::arg("head_dim"),
@@ -1615,7 +1654,8 @@ void bind_runners(py::module_& m) {
            py::arg("activations_fp8") = false, py::arg("qkv_z") = py::none(), py::arg("o_z") = py::none(),
            py::arg("gate_up_z") = py::none(), py::arg("down_z") = py::none(), py::arg("router_w") = py::none(),
            py::arg("experts_gate_up_w") = py::none(), py::arg("experts_down_w") = py::none(),
-           py::arg("experts_per_token") = 0, py::arg("norm_topk") = false)
+           py::arg("experts_per_token") = 0, py::arg("norm_topk") = false,
+           py::arg("experts_gate_up_s") = py::none(), py::arg("experts_down_s") = py::none())
       .def("forward", &LlamaRunner::forward, py::call_guard<py::gil_scoped_release>());
   py::class_<BertRunner>(m, "BertRunner")
       .def(py::init<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<std::vector<at::Tensor>>,

@@ -220,9 +220,14 @@ def moe_route(x, router_w, k: int, norm_topk: bool):
     return ids.to(torch.int32).contiguous(), w.to(torch.float32).contiguous()
 
 
-def moe_mlp(x, router_w, gate_up_w, down_w, k: int, norm_topk: bool, route=None, slots: bool = False):
+def moe_mlp(x, router_w, gate_up_w, down_w, k: int, norm_topk: bool, route=None, slots: bool = False,
+            gate_up_s=None, down_s=None):
     """out [T, H] in x's dtype; ``route`` = (topk_ids, topk_w) replaces the router.  With
-    ``slots`` also the per-slot outputs y [T, k, H] (float64 values of x's dtype)."""
+    ``slots`` also the per-slot outputs y [T, k, H] (float64 values of x's dtype).  With the
+    row scales ``gate_up_s`` [E, 2F] / ``down_s`` [E, H] the expert weights are fp8 codes and
+    stand for code * s, formed here in float64."""
+    if (gate_up_s is None) != (down_s is None):
+        raise ValueError("moe_mlp: gate_up_s and down_s are given together or not at all")
     ids, w = route if route is not None else moe_route(x, router_w, k, norm_topk)
     T, H = x.shape
     F = down_w.shape[2]
@@ -230,9 +235,12 @@ def moe_mlp(x, router_w, gate_up_w, down_w, k: int, norm_topk: bool, route=None,
     y = torch.zeros(T, ids.shape[1], H, dtype=torch.float64, device=x.device)
     for e in ids.unique().tolist():
         t, s = (ids == e).nonzero(as_tuple=True)
-        gu = xd[t] @ gate_up_w[e].double().t()
+        wgu, wdn = gate_up_w[e].double(), down_w[e].double()
+        if gate_up_s is not None:
+            wgu, wdn = wgu * gate_up_s[e].double()[:, None], wdn * down_s[e].double()[:, None]
+        gu = xd[t] @ wgu.t()
         act = (torch.nn.functional.silu(gu[:, :F]) * gu[:, F:]).to(x.dtype).double()
-        y[t, s] = (w[t, s].double()[:, None] * (act @ down_w[e].double().t())).to(x.dtype).double()
+        y[t, s] = (w[t, s].double()[:, None] * (act @ wdn.t())).to(x.dtype).double()
     out = y[:, 0].clone()
     for s in range(1, ids.shape[1]):   # slot order
         out += y[:, s]

@@ -26,7 +26,8 @@ def bench_llm(args):
         import dataclasses
         cfg = dataclasses.replace(cfg, name=cfg.name + "+qkv-bias", qkv_bias=True)
     t0 = time.time()
-    model = LlamaModel(cfg, device="cuda", weights_dtype=args.weights_dtype, activations_dtype=args.activations_dtype)
+    model = LlamaModel(cfg, device="cuda", weights_dtype=args.weights_dtype, activations_dtype=args.activations_dtype,
+                       experts_dtype=args.experts_dtype)
     for layer in model.layers if args.qkv_bias else ():
         layer.qkv_b.normal_(0.0, 0.5)
     sync()
@@ -38,7 +39,7 @@ def bench_llm(args):
     sync()
     print(json.dumps({"event": "graphs", "s": round(time.time() - t0, 2), "blocks": eng.num_blocks,
                       "kv_cache_dtype": eng.kv_cache_dtype, "kv_bytes_per_block": eng.kv_bytes_per_block,
-                      "weights_dtype": eng.stats["weights_dtype"],
+                      "weights_dtype": eng.stats["weights_dtype"], "experts_dtype": eng.stats["experts_dtype"],
                       "activations_dtype": eng.stats["activations_dtype"], "weight_bytes": eng.stats["weight_bytes"]}), flush=True)
     sp = SamplingParams(max_tokens=args.gen, temperature=0.8, top_p=0.95, ignore_eos=True)
     prompts = [[(i * 31 + j) % 1000 + 100 for j in range(args.prompt)] for i in range(args.batch)]
@@ -192,6 +193,8 @@ if __name__ == "__main__":
                          "int4: W4A16 kernels, quantised at load in groups of 128)")
     ap.add_argument("--activations-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="LLM: fp8 (with --weights-dtype fp8) runs steps of more than 4 rows on the W8A8 kernels")
+    ap.add_argument("--experts-dtype", choices=("bf16", "fp8"), default="bf16",
+                    help="LLM: fp8 stores the expert matrices of a mixture-of-experts model as e4m3 codes (W8A16 grouped GEMMs)")
     ap.add_argument("--qkv-bias", action="store_true",
                     help="LLM: the model's shape with a random bias on the QKV projection (LlamaConfig.qkv_bias)")
     ap.add_argument("--texts", type=int, default=2048)
