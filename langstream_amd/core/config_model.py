@@ -345,8 +345,11 @@ RESOURCE_MODELS: Dict[str, Model] = {
                            "activations stay bf16; a bf16 checkpoint or preset is quantised at load; bf16 on an "
                            "fp8 checkpoint is refused; an AWQ or GPTQ checkpoint holds int4 weights, 4-bit codes "
                            "with a scale and a zero point per group of input columns, and is served as such under "
-                           "auto, bf16 and fp8 on it are refused); unset: the LS_WEIGHTS_DTYPE environment "
-                           "variable, else auto."),
+                           "auto, bf16 and fp8 on it are refused; mxfp4 quantises a bf16 checkpoint or preset "
+                           "at load to OCP MXFP4, e2m1 codes with one power-of-two scale per 32 input columns, and "
+                           "runs W4A8 on the block-scaled matrix instruction: dense models on one GPU, refused on "
+                           "an fp8 or int4 checkpoint and together with activations-dtype fp8); unset: the "
+                           "LS_WEIGHTS_DTYPE environment variable, else auto."),
         "activations-dtype": S("Element type of the projection inputs: bf16, or fp8 (needs fp8 weights; steps of "
                                "more than 4 rows quantise each projection's input rows to e4m3 with one dynamic "
                                "scale per row and run on the FP8 matrix instructions); unset: the "

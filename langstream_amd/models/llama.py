@@ -230,12 +230,15 @@ def _linear(x: torch.Tensor, w: torch.Tensor, s: Optional[torch.Tensor] = None, 
     is packed int4 codes, ``s`` its group scales, and the W4A16 projection runs (ops.linear_w4)."""
     if z is not None:
         return ops.linear_w4(x, w, s, z)
+    if s is not None and s.dtype == torch.uint8:
+        # MXFP4 codes + E8M0 block scales: W4A8 at every row count (ops.linear_mxfp4; the reference on the CPU)
+        return ops.linear_mxfp4(x, w, s)
     if s is not None:
         return ops.linear_w8a8(x, w, s) if _a8(x, w, a8) else ops.linear_w8(x, w, s)
     return ops.gemm_prefill(x, w) if _pgemm(x, w, False) else F.linear(x, w)
 
 
-WEIGHTS_DTYPES = ("bf16", "fp8", "int4")
+WEIGHTS_DTYPES = ("bf16", "fp8", "int4", "mxfp4")
 INT4_GROUP = ref.INT4_GROUP   # input columns per scale / zero point when a wider weight is quantised here
 ACTIVATIONS_DTYPES = ("bf16", "fp8")
 W8_NAMES = ("qkv", "o", "gate_up", "down")   # the projections an fp8 / int4 model stores as codes + scales
@@ -260,6 +263,13 @@ def int4_group(name: str, N: int, K: int, group: int = INT4_GROUP) -> int:
     return G
 
 
+def mxfp4_check(name: str, N: int, K: int) -> None:
+    """A projection outside the shape rule of the MXFP4 kernels is refused by ``name``, never rerouted."""
+    if N % 128 or K % 128 or K > 28672:
+        raise ValueError(f"{name} {(N, K)}: mxfp4 weights need both dimensions to be multiples of 128 and "
+                         f"K <= 28672 (the shape rule of ops.mx4_supported)")
+
+
 def tp_kv_heads(num_kv_heads: int, world: int) -> int:
     """KV heads per TP rank.  With more ranks than KV heads every KV head is REPLICATED on
     world / num_kv_heads consecutive ranks (each rank keeps the one KV head its query
@@ -273,7 +283,7 @@ def tp_kv_heads(num_kv_heads: int, world: int) -> int:
 
 class LlamaLayer:
     def __init__(self, cfg: LlamaConfig, tp: TPInfo, device, dtype, fp8: bool = False, int4: bool = False,
-                 name: str = "layers.?", experts_fp8: bool = False):
+                 name: str = "layers.?", experts_fp8: bool = False, mxfp4: bool = False):
         H, D = cfg.hidden_size, cfg.head_dim
         assert cfg.num_heads % tp.world == 0, "TP must divide the query heads"
         assert cfg.intermediate_size % tp.world == 0
@@ -320,6 +330,14 @@ class LlamaLayer:
                 G = int4_group(f"{name}.{n}_w", w.shape[0], w.shape[1])
                 for suffix, t in zip(("_w", "_s", "_z"), ref.quantize_weight_int4(w, G)):
                     setattr(self, n + suffix, t)
+        # mxfp4 weights: packed e2m1 codes [N, K / 2] + E8M0 block scales uint8 [N, K / 32]
+        # (ops.reference.quantize_weight_mxfp4), likewise
+        if mxfp4:
+            for n in W8_NAMES:
+                w = getattr(self, n + "_w")
+                mxfp4_check(f"{name}.{n}_w", w.shape[0], w.shape[1])
+                for suffix, t in zip(("_w", "_s"), ref.quantize_weight_mxfp4(w)):
+                    setattr(self, n + suffix, t)
         self.in_norm = torch.ones(H, device=device, dtype=dtype)
         self.post_norm = torch.ones(H, device=device, dtype=dtype)
         # packed like the rows of qkv_w: q heads, k heads, v heads
@@ -360,6 +378,17 @@ class LlamaModel:
         if experts_dtype == "fp8" and not cfg.num_experts:
             raise ValueError(f"experts_dtype='fp8' on a dense model ({cfg.name}): it has no experts; "
                              f"weights_dtype='fp8' quantises its projections")
+        if weights_dtype == "mxfp4":
+            # refused by name, with the reason
+            if activations_dtype == "fp8":
+                raise ValueError("activations_dtype='fp8' with weights_dtype='mxfp4': the MXFP4 projections quantise "
+                                 "their input rows to fp8 themselves (W4A8); leave activations_dtype at 'bf16'")
+            if cfg.num_experts:
+                raise ValueError(f"a mixture-of-experts model ({cfg.name}) with weights_dtype='mxfp4' is not "
+                                 f"supported: there are no MXFP4 expert kernels")
+            if tp is not None and tp.world > 1:
+                raise ValueError(f"weights_dtype='mxfp4' under tensor parallelism (world {tp.world}) is not "
+                                 f"supported: the block scales are not sharded yet")
         if cfg.num_experts:
             # refused by name, never silently served
             if weights_dtype != "bf16" or activations_dtype != "bf16":
@@ -383,7 +412,9 @@ class LlamaModel:
         # "fp8": the four projections of every layer are float8_e4m3fn codes with one f32 scale
         # per output row (W8A16: activations, embed, lm_head and the norms keep `dtype`).
         # "int4": they are packed 4-bit codes with an f32 scale and a zero point per group of
-        # input columns (W4A16, ops/csrc/gemm_w4.hip; the AWQ / GPTQ family)
+        # input columns (W4A16, ops/csrc/gemm_w4.hip; the AWQ / GPTQ family).
+        # "mxfp4": they are packed e2m1 codes with one E8M0 scale per 32 input columns and every
+        # projection quantises its input rows to e4m3 (W4A8, ops/csrc/gemm_mx4.hip)
         self.weights_dtype = weights_dtype
         # "fp8": the two stacked expert matrices of every mixture-of-experts layer are float8_e4m3fn
         # codes with one f32 scale per (expert, output row) and the grouped GEMMs run W8A16
@@ -403,7 +434,7 @@ class LlamaModel:
             self.embed = (torch.randn(self.vocab_per_rank, H, device=self.device) * 0.02).to(dtype)
             self.layers = [LlamaLayer(cfg, self.tp, self.device, dtype, fp8=weights_dtype == "fp8",
                                       int4=weights_dtype == "int4", name=f"layers.{i}",
-                                      experts_fp8=experts_dtype == "fp8")
+                                      experts_fp8=experts_dtype == "fp8", mxfp4=weights_dtype == "mxfp4")
                            for i in range(cfg.num_layers)]
             self.final_norm = torch.ones(H, device=self.device, dtype=dtype)
             self.lm_head = self.embed if cfg.tie_embeddings else (
@@ -443,7 +474,7 @@ class LlamaModel:
             names += ("q_norm", "k_norm")
         if self.experts_dtype == "fp8":
             names += tuple(n + "_s" for n in EXPERT_NAMES)
-        if self.weights_dtype in ("fp8", "int4"):
+        if self.weights_dtype in ("fp8", "int4", "mxfp4"):
             names += tuple(n + "_s" for n in W8_NAMES)
         if self.weights_dtype == "int4":
             names += tuple(n + "_z" for n in W8_NAMES)
@@ -463,11 +494,11 @@ class LlamaModel:
         self.final_norm.copy_(sd["final_norm"])
         if not self.cfg.tie_embeddings:
             self.lm_head.copy_(sd["lm_head"])
-        fp8, int4 = self.weights_dtype == "fp8", self.weights_dtype == "int4"
+        fp8, int4, mxfp4 = (self.weights_dtype == d for d in ("fp8", "int4", "mxfp4"))
         for i, l in enumerate(self.layers):
             for n in self._layer_names():
                 key = f"layers.{i}.{n}"
-                if (fp8 or int4) and n.endswith(("_s", "_z")):
+                if (fp8 or int4 or mxfp4) and n.endswith(("_s", "_z")):
                     continue   # loaded with its weight below
                 if n[:-2] in EXPERT_NAMES:
                     if n.endswith("_w"):
@@ -482,6 +513,12 @@ class LlamaModel:
                     if int4:
                         self._load_int4(l, n[:-2], key, sd)
                         continue
+                    if mxfp4:
+                        self._load_mxfp4(l, n[:-2], key, sd)
+                        continue
+                    if src.dtype == torch.uint8:
+                        raise ValueError(f"{key} holds MXFP4 codes (uint8) but the model's weights_dtype is "
+                                         f"{self.weights_dtype!r}; build the model with weights_dtype='mxfp4'")
                     if not fp8 and ref.is_fp8(src):
                         raise ValueError(f"{key} holds float8_e4m3fn codes but the model's weights_dtype is "
                                          f"'bf16'; build the model with weights_dtype='fp8'")
@@ -555,6 +592,31 @@ class LlamaModel:
             setattr(layer, n + suffix, v.to(self.device).contiguous())
         self._runner = None
 
+    def _load_mxfp4(self, layer: LlamaLayer, n: str, key: str, sd: dict) -> None:
+        """One projection of an mxfp4 model: the (codes, scales) pair of the state dict as it is, or
+        a wider weight quantised here with the one rule."""
+        src, skey, dst = sd[key], key[:-2] + "_s", getattr(layer, n + "_w")
+        N, K = dst.shape[0], 2 * dst.shape[1]
+        if ref.is_fp8(src):
+            raise ValueError(f"{key} holds float8_e4m3fn codes but the model's weights_dtype is 'mxfp4'")
+        if src.dtype == torch.uint8:
+            if skey not in sd:
+                raise ValueError(f"{key} holds MXFP4 codes but {skey} is missing")
+            sc = sd[skey]
+            if tuple(src.shape) != (N, K // 2) or tuple(sc.shape) != (N, K // 32):
+                raise ValueError(f"{key} / {skey} have shapes {tuple(src.shape)} / {tuple(sc.shape)}, expected "
+                                 f"packed codes {(N, K // 2)} and block scales {(N, K // 32)}")
+            ref.check_scales_mxfp4(sc, skey)
+            codes = src
+        elif skey in sd:
+            raise ValueError(f"{skey} is present but {key} holds {src.dtype}, not MXFP4 codes")
+        else:
+            if tuple(src.shape) != (N, K):
+                raise ValueError(f"{key} has shape {tuple(src.shape)}, expected {(N, K)}")
+            codes, sc = ref.quantize_weight_mxfp4(src.to(self.device))
+        dst.copy_(codes)
+        getattr(layer, n + "_s").copy_(sc)
+
     # ------------------------------------------------------------------ forward
     def embed_tokens(self, ids: torch.Tensor) -> torch.Tensor:
         if self.tp.world == 1:
@@ -608,7 +670,11 @@ class LlamaModel:
                 a = None
             elif layer.gate_up_s is not None:
                 gu = _linear(o, layer.gate_up_w, layer.gate_up_s, a8, layer.gate_up_z)
-                if _a8(gu, layer.down_w, a8):
+                if self.weights_dtype == "mxfp4":
+                    # the row quantiser forms bf16(silu(g) * u) itself at every row count
+                    d = ops.linear_mxfp4(gu, layer.down_w, layer.down_s, silu_mul=True)
+                    a = None
+                elif _a8(gu, layer.down_w, a8):
                     # the quantiser forms bf16(silu(g) * u) itself: no [T, F] intermediate
                     d = ops.linear_w8a8(gu, layer.down_w, layer.down_s, silu_mul=True)
                     a = None
@@ -648,8 +714,9 @@ class LlamaModel:
             [self.cfg.layer_window(i) for i in range(len(L))],
             [l.q_norm for l in L] if self.cfg.qk_norm else None,
             [l.k_norm for l in L] if self.cfg.qk_norm else None,
-            *([[getattr(l, n + "_s") for l in L] for n in W8_NAMES] if self.weights_dtype in ("fp8", "int4") else []),
-            activations_fp8=self.activations_dtype == "fp8",
+            *([[getattr(l, n + "_s") for l in L] for n in W8_NAMES]
+              if self.weights_dtype in ("fp8", "int4", "mxfp4") else []),
+            activations_fp8=self.activations_dtype == "fp8", weights_mxfp4=self.weights_dtype == "mxfp4",
             **({n + "_z": [getattr(l, n + "_z") for l in L] for n in W8_NAMES} if self.weights_dtype == "int4" else {}),
             **(dict(router_w=[l.router_w for l in L], experts_gate_up_w=[l.experts_gate_up_w for l in L],
                     experts_down_w=[l.experts_down_w for l in L], experts_per_token=self.cfg.experts_per_token,

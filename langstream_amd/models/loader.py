@@ -517,10 +517,13 @@ def _cat_rows(ts) -> torch.Tensor:
 
 def checkpoint_weights_dtype(sd: Dict[str, torch.Tensor]) -> str:
     """"fp8" when the layer projections of a packed state dict are float8_e4m3fn codes, "int4"
-    when they are packed 4-bit codes with zero points (``{name}_z``), else "bf16"."""
+    when they are packed 4-bit codes with zero points (``{name}_z``), "mxfp4" when they are uint8
+    codes without zero points (packed e2m1 with E8M0 block scales ``{name}_s``), else "bf16"."""
     if any(k.endswith(tuple(f".{n}_z" for n in W8_NAMES)) for k in sd):
         return "int4"
     keys = tuple(f".{n}_w" for n in W8_NAMES)
+    if any(k.endswith(keys) and v.dtype == torch.uint8 for k, v in sd.items()):
+        return "mxfp4"
     return "fp8" if any(k.endswith(keys) and v.dtype == FP8 for k, v in sd.items()) else "bf16"
 
 

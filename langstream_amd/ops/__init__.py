@@ -245,11 +245,58 @@ def w4_supported(w) -> bool:
             and w.shape[0] % 64 == 0 and w.shape[1] >= 32 and w.shape[1] % 32 == 0)
 
 
+def mx4_gemm(xq, xs, w, s, out=None, splits: int = 0):
+    """The block-scaled GEMM of linear_mxfp4 on rows that are quantised already: e4m3 codes xq
+    [M, K] with f32 row scales xs (quantize_rows_fp8) times MXFP4 weights (w, s) -> bf16 [M, N].
+    M <= 16 runs on mx4_skinny, everything else on the tiled mx4_gemm; ``splits`` > 0 forces
+    that many K slices (clamped to the K steps and to 16)."""
+    if _gpu(xq, w, s):
+        h = hip()
+        M, N, K = xq.shape[0], w.shape[0], 2 * w.shape[1]
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=xq.device) if out is None else out
+        need = splits * M * N * 4 if splits > 0 else (h.mx4_gemm_workspace(M, N, K) if N >= 128 and K >= 128 else 0)
+        h.mx4_gemm(out, xq, xs, w, s, _w8_workspace(xq.device, need), splits)
+        return out
+    r = ((xq.float() @ ref.dequantize_weight_mxfp4(w, s).t()) * xs.float()[:, None]).to(torch.bfloat16)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
+def linear_mxfp4(x, w, s, out=None, splits: int = 0, silu_mul: bool = False):
+    """MXFP4 projection (W4A8, ops/csrc/gemm_mx4.hip): the rows of bf16 x [M, K] (``silu_mul``:
+    silu_and_mul of x [M, 2K]) quantised to e4m3 with one f32 scale per row, times packed e2m1
+    codes w uint8 [N, K / 2] with E8M0 block scales s uint8 [N, K / 32] (the pair of
+    ops.reference.quantize_weight_mxfp4) on the block-scaled MFMA.  N % 128 == 0, K % 128 == 0
+    and K <= 28672; anything else raises."""
+    if _gpu(x, w, s):
+        h = hip()
+        M, N, K = x.shape[0], w.shape[0], 2 * w.shape[1]
+        out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+        need = splits * M * N * 4 if splits > 0 else (h.mx4_gemm_workspace(M, N, K) if N >= 128 and K >= 128 else 0)
+        h.linear_mxfp4(out, x, w, s, _w8_workspace(x.device, need), splits, silu_mul)
+        return out
+    r = ref.linear_mxfp4(x, w, s, silu_mul=silu_mul)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
+def mx4_supported(w) -> bool:
+    """The shape rule of the MXFP4 kernels: contiguous uint8 [N, K / 2], N % 128 == 0, K % 128 == 0,
+    K <= 28672 (the same rule on the CPU, so a model is refused alike on both)."""
+    return (w.dim() == 2 and w.dtype == torch.uint8 and w.is_contiguous() and w.shape[0] >= 128
+            and w.shape[0] % 128 == 0 and w.shape[1] >= 64 and w.shape[1] % 64 == 0 and 2 * w.shape[1] <= 28672)
+
+
 def w8_launch_counts(reset: bool = False) -> dict:
     """Launches of the W8 kernels per variant since the last reset: {"gemv": n,
     "gemm_bm64_s4": n, ...} (tile rows and K slices of w8_gemm), of the W8A8 kernels:
     "a8_bm128_s2" (tile rows and K slices of w8a8_gemm), "quant", "quant_silu", and of the W4
-    kernels: "w4_gemv", "w4_bm64_s4" (tile rows and K slices of w4_gemm)."""
+    kernels: "w4_gemv", "w4_bm64_s4" (tile rows and K slices of w4_gemm), and of the MXFP4 kernels:
+    "mx4_skinny_s2", "mx4_bm128_s1" (form or tile rows, and K slices, of mx4_gemm)."""
     return dict(hip().w8_launch_counts(reset))
 
 

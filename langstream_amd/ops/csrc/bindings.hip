@@ -113,6 +113,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w4_gemv", &w4_gemv);
   m.def("linear_w4", &linear_w4, py::arg("out"), py::arg("x"), py::arg("w"), py::arg("s"), py::arg("z"),
         py::arg("workspace"), py::arg("splits") = 0);
+  m.def("mx4_supported", &mx4_supported);
+  m.def("mx4_gemm_workspace", &mx4_gemm_workspace);
+  m.def("mx4_gemm", &mx4_gemm, py::arg("out"), py::arg("xq"), py::arg("xs"), py::arg("w"), py::arg("s"),
+        py::arg("workspace"), py::arg("splits") = 0);
+  m.def("linear_mxfp4", &linear_mxfp4, py::arg("out"), py::arg("x"), py::arg("w"), py::arg("s"), py::arg("workspace"),
+        py::arg("splits") = 0, py::arg("silu_mul") = false);
   m.def("moe_supported", &moe_supported);
   m.def("moe_route", &moe_route);
   m.def("moe_experts", &moe_experts, py::arg("out"), py::arg("x"), py::arg("gate_up_w"), py::arg("down_w"),

@@ -412,5 +412,6 @@ pybind11::dict w8_launch_counts(bool reset) {
     }
   w8a8_launch_counts(d, reset);   // a8_bm{BM}_s{S}, quant, quant_silu (gemm_w8a8.hip)
   w4_launch_counts(d, reset);     // w4_gemv, w4_bm{BM}_s{S} (gemm_w4.hip)
+  mx4_launch_counts(d, reset);    // mx4_skinny_s{S}, mx4_bm{BM}_s{S} (gemm_mx4.hip)
   return d;
 }

@@ -282,6 +282,17 @@ void linear_w4(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s, at::Ten
                int64_t splits_force);
 void w4_launch_counts(pybind11::dict& d, bool reset);   // adds its keys to the census of w8_launch_counts
 
+// ----------------------------------------------------------------------- gemm_mx4.hip
+// MXFP4 projections (W4A8): packed e2m1 codes uint8 [N, K / 2] with E8M0 block scales uint8 [N, K / 32],
+// times per-row e4m3fn activation codes, on the block-scaled MFMA.
+bool mx4_supported(const at::Tensor& w);
+int64_t mx4_gemm_workspace(int64_t M, int64_t N, int64_t K);
+void mx4_gemm(at::Tensor out, at::Tensor xq, at::Tensor xs, at::Tensor w, at::Tensor s, at::Tensor workspace,
+              int64_t splits_force);
+void linear_mxfp4(at::Tensor out, at::Tensor x, at::Tensor w, at::Tensor s, at::Tensor workspace, int64_t splits_force,
+                  bool silu_mul);
+void mx4_launch_counts(pybind11::dict& d, bool reset);   // adds its keys to the census of w8_launch_counts
+
 // ---------------------------------------------------------------------------- moe.hip
 // Sparse mixture-of-experts MLP: router_w [E, H], gate_up_w [E, 2F, H], down_w [E, H, F], all bf16;
 // topk_ids int32 / topk_w f32 [T, k].  With gate_up_s f32 [E, 2F] and down_s f32 [E, H] the two expert

@@ -112,7 +112,7 @@ class LlamaRunner {
               c10::optional<std::vector<at::Tensor>> experts_gate_up_w = c10::nullopt,
               c10::optional<std::vector<at::Tensor>> experts_down_w = c10::nullopt, int64_t experts_per_token = 0,
               bool norm_topk = false, c10::optional<std::vector<at::Tensor>> experts_gate_up_s = c10::nullopt,
-              c10::optional<std::vector<at::Tensor>> experts_down_s = c10::nullopt)
+              c10::optional<std::vector<at::Tensor>> experts_down_s = c10::nullopt, bool weights_mxfp4 = false)
       : embed_(embed), qkv_w_(qkv_w), o_w_(o_w), gate_up_w_(gate_up_w), down_w_(down_w), in_norm_(in_norm),
         post_norm_(post_norm), final_norm_(final_norm), lm_head_(lm_head), kc_(k_caches), vc_(v_caches),
         cos_sin_(cos_sin), hq_(hq), hkv_(hkv), d_(head_dim), eps_(eps), scale_(scale), vocab_(vocab_size),
@@ -243,7 +243,41 @@ class LlamaRunner {
                   "LlamaRunner: the zero points qkv_z, o_z, gate_up_z and down_z are given together, with the four "
                   "weight scale lists, or not at all");
       w4_ = zgiven == 4;
-      if (w4_) {
+      // MXFP4 projection weights (W4A8, gemm_mx4.hip): the mode is the constructor's flag, never
+      // inferred from dtypes; the four scale lists are then the uint8 E8M0 block scales [N, K / 32]
+      // and the layers run the plain sequence of fp8 weights, every projection through linear_mxfp4
+      mx4_ = weights_mxfp4;
+      TORCH_CHECK(!mx4_ || (w8_ && !w4_), "LlamaRunner: mxfp4 weights come with the four block-scale lists qkv_s, o_s, "
+                  "gate_up_s and down_s, and without zero points");
+      if (mx4_) {
+        TORCH_CHECK(!activations_fp8, "LlamaRunner: fp8 activations with mxfp4 weights: the MXFP4 projections quantise "
+                    "their input rows themselves");
+        TORCH_CHECK(process_group.is_none(), "LlamaRunner: mxfp4 weights under tensor parallelism are not supported");
+        qkv_s_ = *qkv_s;
+        o_s_ = *o_s;
+        gate_up_s_ = *gate_up_s;
+        down_s_ = *down_s;
+        const std::vector<at::Tensor>* ss[4] = {&qkv_s_, &o_s_, &gate_up_s_, &down_s_};
+        int64_t wsz = 0;
+        for (int k = 0; k < 4; ++k) {
+          TORCH_CHECK(ss[k]->size() == L, "LlamaRunner: one ", names[k], " block-scale tensor per layer");
+          for (size_t l = 0; l < L; ++l) {
+            const at::Tensor& w = (*wl[k])[l];
+            const at::Tensor& sc = (*ss[k])[l];
+            TORCH_CHECK(w.is_cuda() && mx4_supported(w), "LlamaRunner: layers.", l, ".", names[k],
+                        " is not a contiguous uint8 [N, K / 2] with N % 128 == 0, K % 128 == 0 and K <= 28672 (shape ",
+                        w.sizes(), ", ", w.scalar_type(), "): the MXFP4 kernels do not take it");
+            const int64_t N = w.size(0), K = 2 * w.size(1);
+            TORCH_CHECK(sc.is_cuda() && sc.device() == w.device() && sc.scalar_type() == at::kByte &&
+                            sc.is_contiguous() && sc.dim() == 2 && sc.size(0) == N && sc.size(1) == K / 32,
+                        "LlamaRunner: the block scales of layers.", l, ".", names[k], " must be a contiguous uint8 [", N,
+                        ", ", K / 32, "] on the device of the weight");
+            wsz = std::max(wsz, mx4_gemm_workspace(int64_t(1) << 20, N, K));
+          }
+        }
+        // split-K partials of mx4_gemm, sized once for every row count so graph captures never allocate
+        w8_ws_ = at::empty({std::max<int64_t>(wsz / 4, 4)}, embed_.options().dtype(at::kFloat));
+      } else if (w4_) {
         TORCH_CHECK(!activations_fp8, "LlamaRunner: fp8 activations need fp8 weights, not int4");
         qkv_s_ = *qkv_s;
         o_s_ = *o_s;
@@ -484,11 +518,14 @@ class LlamaRunner {
   // linear_w8.  T <= 4 keeps the W8A16 GEMV: it streams each weight byte once and is
   // bandwidth-bound there, so FP8 activations would add a quantiser launch and buy nothing.
   bool a8_route(int64_t T, const at::Tensor& w) const { return a8_ && T > 4 && w8a8_supported(w); }
+  // mxfp4 weights (mx4_): s holds the E8M0 block scales and every row count goes through
+  // linear_mxfp4 (gemm_mx4.hip): the row quantiser, then mx4_skinny at T <= 16, else the tiles.
   // int4 weights (w4_): z holds the layer's zero points and every row count goes through
   // linear_w4 (gemm_w4.hip): w4_gemv at T <= 4 where its shape rule holds, else w4_gemm.
   at::Tensor proj_w8(const at::Tensor& x, const at::Tensor& w, const at::Tensor& s, const at::Tensor& z) {
     at::Tensor out = at::empty({x.size(0), w.size(0)}, x.options());
-    if (w4_) linear_w4(out, x, w, s, z, w8_ws_, 0);
+    if (mx4_) linear_mxfp4(out, x, w, s, w8_ws_, 0, false);
+    else if (w4_) linear_w4(out, x, w, s, z, w8_ws_, 0);
     else if (a8_route(x.size(0), w)) linear_w8a8(out, x, w, s, w8_ws_, 0);
     else linear_w8(out, x, w, s, w8_ws_, 0);
     return out;
@@ -498,6 +535,11 @@ class LlamaRunner {
   // intermediate never goes to memory.
   at::Tensor proj_w8_silu(const at::Tensor& gu, const at::Tensor& w, const at::Tensor& s, const at::Tensor& z) {
     const int64_t T = gu.size(0), F = gu.size(1) / 2;
+    if (mx4_) {   // mxfp4 weights: the same at every row count
+      at::Tensor out = at::empty({T, w.size(0)}, gu.options());
+      linear_mxfp4(out, gu, w, s, w8_ws_, 0, true);
+      return out;
+    }
     if (a8_route(T, w)) {
       at::Tensor out = at::empty({T, w.size(0)}, gu.options());
       at::Tensor xq = at::empty({T, F}, gu.options().dtype(at::kFloat8_e4m3fn));
@@ -997,6 +1039,7 @@ class LlamaRunner {
   std::vector<at::Tensor> qkv_s_, o_s_, gate_up_s_, down_s_;   // per-layer f32 row scales of fp8 weights, empty without
   bool w8_ = false;            // the four projections of every layer are quantised: fp8 codes + row scales, or int4 (w4_)
   std::vector<at::Tensor> qkv_z_, o_z_, gate_up_z_, down_z_;   // per-layer uint8 zero points of int4 weights, empty without
+  bool mx4_ = false;           // the projections are MXFP4: packed e2m1 codes with E8M0 block scales [N, K / 32] (gemm_mx4.hip)
   bool w4_ = false;            // the projections are 4-bit codes with f32 scales and zero points [N, K / G]
   at::Tensor w8_ws_;           // split-K workspace of w8_gemm / w8a8_gemm
   bool a8_ = false;            // fp8 activations: T > 4 projections on the W8A8 kernels (gemm_w8a8.hip)
@@ -1642,7 +1685,7 @@ void bind_runners(py::module_& m) {
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
                     c10::optional<std::vector<at::Tensor>>, int64_t, bool, c10::optional<std::vector<at::Tensor>>,
-                    c10::optional<std::vector<at::Tensor>>>(),
+                    c10::optional<std::vector<at::Tensor>>, bool>(),
            py::arg("embed"), py::arg("qkv_w"), py::arg("o_w"), py::arg("gate_up_w"), py::arg("down_w"),
            py::arg("in_norm"), py::arg("post_norm"), py::arg("final_norm"), py::arg("lm_head"), py::arg("k_caches"),
            py::arg("v_caches"), py::arg("cos_sin"), py::arg("hq"), py::arg("hkv"), py::arg("head_dim"),
@@ -1655,7 +1698,8 @@ void bind_runners(py::module_& m) {
            py::arg("gate_up_z") = py::none(), py::arg("down_z") = py::none(), py::arg("router_w") = py::none(),
            py::arg("experts_gate_up_w") = py::none(), py::arg("experts_down_w") = py::none(),
            py::arg("experts_per_token") = 0, py::arg("norm_topk") = false,
-           py::arg("experts_gate_up_s") = py::none(), py::arg("experts_down_s") = py::none())
+           py::arg("experts_gate_up_s") = py::none(), py::arg("experts_down_s") = py::none(),
+           py::arg("weights_mxfp4") = false)
       .def("forward", &LlamaRunner::forward, py::call_guard<py::gil_scoped_release>());
   py::class_<BertRunner>(m, "BertRunner")
       .def(py::init<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<std::vector<at::Tensor>>,

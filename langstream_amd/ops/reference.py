@@ -167,6 +167,70 @@ def linear_w8a8(x, codes, ws, dtype=None, silu_mul: bool = False):
                      x.dtype if x.dtype in (torch.bfloat16, torch.float16) else torch.float32)
 
 
+# ---- MXFP4 projection weights (opt-in, W4A8; OCP microscaling).  A quantised projection [N, K]
+# is a pair: codes uint8 [N, K / 2], byte j of a row = q[2j] | q[2j + 1] << 4 (low nibble first:
+# the order of OCP MX and of torch.float4_e2m1fn_x2), a code e2m1 (bit 3 the sign, magnitudes
+# E2M1_VALUES), and scales uint8 [N, K / 32], E8M0: byte b means 2^(b - 127); 255 (NaN) is never
+# produced and is refused.
+#   w[n, k] = value(q[n, k]) * 2^(scales[n, k // 32] - 127)
+#   y[m, n] = bf16(xs[m] * sum_k code_x[m, k] * w[n, k])   with (code_x, xs) = quantize_rows_fp8(x)
+MX_BLOCK = 32
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_weight_mxfp4(w):
+    """(codes, scales) of a [N, K] weight (any float dtype, K % 32 == 0) by the OCP rule in f32: per
+    block of 32, e = clamp(floor(log2(amax)) - 2, -127, 127) (a zero block: e = 0), byte e + 127;
+    a code is the e2m1 value nearest to clamp(w * 2^-e, -6, 6), ties to the even code."""
+    N, K = w.shape
+    if K % MX_BLOCK:
+        raise ValueError(f"MXFP4 blocks are {MX_BLOCK} input columns; K = {K} is not a multiple")
+    wf = w.float().view(N, K // MX_BLOCK, MX_BLOCK)
+    amax = wf.abs().amax(2)
+    ex = torch.frexp(amax)[1]                      # amax = m * 2^ex, m in [0.5, 1): floor(log2) = ex - 1
+    e = torch.where(amax > 0, (ex - 3).clamp(-127, 127), torch.zeros_like(ex))
+    v = torch.ldexp(wf, -e[:, :, None]).clamp(-6.0, 6.0)
+    a = v.abs()
+    # the midpoints between neighbouring magnitudes; a tie goes to the even code of the two
+    q = ((a > 0.25).int() + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0))
+    q = (q | (((v < 0) & (q > 0)).int() << 3)).to(torch.uint8).view(N, K // 2, 2)
+    return (q[:, :, 0] | (q[:, :, 1] << 4)).contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def check_scales_mxfp4(scales, name: str = "scales") -> None:
+    """E8M0 byte 255 is NaN: refused wherever the host sees the scales."""
+    if scales.dtype != torch.uint8:
+        raise ValueError(f"{name} must be uint8 E8M0 block scales, got {scales.dtype}")
+    if scales.numel() and int(scales.max()) == 255:
+        raise ValueError(f"{name} holds the E8M0 byte 255 (NaN)")
+
+
+def dequantize_weight_mxfp4(codes, scales, dtype=torch.float32):
+    """value(q) * 2^(scale - 127) as `dtype` [N, K] (exact in f32 and f64)."""
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    if codes.dtype != torch.uint8 or tuple(scales.shape) != (N, K // MX_BLOCK):
+        raise ValueError(f"MXFP4 codes must be uint8 [N, K / 2] with scales [N, K / {MX_BLOCK}], got "
+                         f"{codes.dtype} {tuple(codes.shape)} and {tuple(scales.shape)}")
+    check_scales_mxfp4(scales)
+    q = torch.stack([codes & 15, codes >> 4], 2).view(N, K).long()
+    ct = dtype if dtype in (torch.float32, torch.float64) else torch.float32
+    lut = torch.tensor(E2M1_VALUES + tuple(-x for x in E2M1_VALUES), dtype=ct, device=codes.device)
+    e = (scales.to(torch.int32) - 127).repeat_interleave(MX_BLOCK, 1)
+    return torch.ldexp(lut[q], e).to(dtype)
+
+
+def linear_mxfp4(x, codes, scales, dtype=None, silu_mul: bool = False):
+    """The MXFP4 projection on the CPU and the oracle: quantize_rows_fp8, the product with the
+    dequantised weight accumulated in f32 (or `dtype`, float64 for an oracle), times xs; returns
+    x's dtype for bf16 / f16 x with the default compute, else the compute dtype."""
+    xq, xs = quantize_rows_fp8(x, silu_mul)
+    ct = dtype or torch.float32
+    y = (xq.to(ct) @ dequantize_weight_mxfp4(codes, scales, ct).t()) * xs.to(ct)[:, None]
+    if dtype is None and x.dtype in (torch.bfloat16, torch.float16):
+        return y.to(x.dtype)
+    return y
+
+
 def rmsnorm(x, w, eps):
     xf = x.float()
     return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * w.float()).to(x.dtype)

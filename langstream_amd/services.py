@@ -18,12 +18,15 @@ Configuration (``local-gpu-configuration`` resource):
   max-model-len (4096), max-prefill-tokens (16384), kv-fraction (0.55), use-graphs (true),
   kv-cache-dtype (auto | bf16 | fp8; unset: the LS_KV_CACHE_DTYPE environment variable, else auto),
   kv-k-scale / kv-v-scale (1.0; the two scalars of an fp8 KV cache),
-  weights-dtype (auto | bf16 | fp8; unset: the LS_WEIGHTS_DTYPE environment variable, else auto.
+  weights-dtype (auto | bf16 | fp8 | mxfp4; unset: the LS_WEIGHTS_DTYPE environment variable, else auto.
   auto: what the checkpoint holds, bf16 for presets; fp8 on a bf16 checkpoint or preset quantises
   the four projections of every layer at load, e4m3 codes with one scale per output row; bf16 on an
   fp8 checkpoint is refused.  An AWQ or GPTQ checkpoint holds int4 weights -- 4-bit codes with a scale
   and a zero point per group of input columns -- and is served as such under auto; bf16 and fp8 on it
-  are refused),
+  are refused.  mxfp4 on a bf16 checkpoint or preset quantises the four projections at load to OCP
+  MXFP4 -- e2m1 codes with one power-of-two scale per 32 input columns -- and every projection
+  quantises its input rows to fp8 (W4A8); dense models on one GPU only; refused on an fp8 or int4
+  checkpoint),
   activations-dtype (bf16 | fp8; unset: the LS_ACTIVATIONS_DTYPE environment variable, else bf16.
   fp8 needs fp8 weights: steps of more than 4 rows quantise each projection's input rows to e4m3
   with one dynamic scale per row and run on the FP8 matrix instructions; never set by a checkpoint),
@@ -173,8 +176,8 @@ class ServiceRegistry:
                     c["use-graphs"] = "false"
             log.info("starting LLM engine %s on %s", name, device)
             wd = str(c.get("weights-dtype") or os.environ.get("LS_WEIGHTS_DTYPE") or "auto").lower()
-            if wd not in ("auto", "bf16", "fp8"):
-                raise ValueError(f"weights-dtype {wd!r}: expected auto, bf16 or fp8")
+            if wd not in ("auto", "bf16", "fp8", "mxfp4"):
+                raise ValueError(f"weights-dtype {wd!r}: expected auto, bf16, fp8 or mxfp4")
             sd = None
             if model_path or c.get("weights-path"):
                 from .models.loader import checkpoint_weights_dtype, load_packed, shard_llama
@@ -189,6 +192,12 @@ class ServiceRegistry:
                 if wd == "fp8" and held == "int4":
                     raise ValueError("weights-dtype fp8: the checkpoint holds int4 (AWQ / GPTQ) projection "
                                      "weights, which are not requantised; use auto")
+                if wd == "mxfp4" and held in ("fp8", "int4"):
+                    raise ValueError(f"weights-dtype mxfp4: the checkpoint holds {held} projection weights, which "
+                                     f"are not requantised; use auto")
+                if wd in ("bf16", "fp8") and held == "mxfp4":
+                    raise ValueError(f"weights-dtype {wd}: the checkpoint holds mxfp4 projection weights, which are "
+                                     f"not widened or requantised; use auto or mxfp4")
                 wd = held if wd == "auto" else wd
                 if self.tp is not None and self.tp.world > 1:
                     sd = shard_llama(sd, mcfg, self.tp.rank, self.tp.world)

@@ -188,9 +188,9 @@ if __name__ == "__main__":
     ap.add_argument("--prefill-chunk", type=int, default=16384)
     ap.add_argument("--kv-dtype", choices=("auto", "bf16", "fp8"), default="auto",
                     help="KV cache element type of the LLM engine (LLMEngine kv_cache_dtype)")
-    ap.add_argument("--weights-dtype", choices=("bf16", "fp8", "int4"), default="bf16",
+    ap.add_argument("--weights-dtype", choices=("bf16", "fp8", "int4", "mxfp4"), default="bf16",
                     help="LLM: element type of the layer projections (LlamaModel weights_dtype; fp8: W8A16 kernels, "
-                         "int4: W4A16 kernels, quantised at load in groups of 128)")
+                         "int4: W4A16 kernels, quantised at load in groups of 128, mxfp4: W4A8 kernels, quantised at load)")
     ap.add_argument("--activations-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="LLM: fp8 (with --weights-dtype fp8) runs steps of more than 4 rows on the W8A8 kernels")
     ap.add_argument("--experts-dtype", choices=("bf16", "fp8"), default="bf16",
