@@ -354,11 +354,12 @@ RESOURCE_MODELS: Dict[str, Model] = {
                                "more than 4 rows quantise each projection's input rows to e4m3 with one dynamic "
                                "scale per row and run on the FP8 matrix instructions); unset: the "
                                "LS_ACTIVATIONS_DTYPE environment variable, else bf16."),
-        "experts-dtype": S("Element type of the expert matrices of a mixture-of-experts model: bf16, or fp8 (e4m3 "
-                           "codes with one scale per expert and output row, quantised at load; activations, the "
-                           "router and every other weight keep their type; refused on a dense model and together "
-                           "with fp8 weights or activations); unset: the LS_EXPERTS_DTYPE environment variable, "
-                           "else bf16."),
+        "experts-dtype": S("Element type of the expert matrices of a mixture-of-experts model: bf16, fp8 (e4m3 "
+                           "codes with one scale per expert and output row) or int4 (4-bit codes with a scale and "
+                           "a zero point per expert, output row and group of 128 input columns), quantised at "
+                           "load; activations, the router and every other weight keep their type; refused on a "
+                           "dense model and together with fp8 weights or activations; unset: the "
+                           "LS_EXPERTS_DTYPE environment variable, else bf16."),
         "sliding-window": B("Serve a model-path with an active sliding window (Mistral, Qwen2 with "
                             "use_sliding_window) over its whole position range, with windowed attention in the "
                             "layers that have a window; false serves only the positions up to the window, with "

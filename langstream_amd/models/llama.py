@@ -242,8 +242,8 @@ WEIGHTS_DTYPES = ("bf16", "fp8", "int4", "mxfp4")
 INT4_GROUP = ref.INT4_GROUP   # input columns per scale / zero point when a wider weight is quantised here
 ACTIVATIONS_DTYPES = ("bf16", "fp8")
 W8_NAMES = ("qkv", "o", "gate_up", "down")   # the projections an fp8 / int4 model stores as codes + scales
-EXPERTS_DTYPES = ("bf16", "fp8")
-EXPERT_NAMES = ("experts_gate_up", "experts_down")   # the stacked expert matrices experts_dtype="fp8" stores as codes + scales
+EXPERTS_DTYPES = ("bf16", "fp8", "int4")
+EXPERT_NAMES = ("experts_gate_up", "experts_down")   # the stacked expert matrices experts_dtype="fp8" / "int4" stores as codes + scales
 
 
 def quantize_experts_fp8(w: torch.Tensor):
@@ -261,6 +261,15 @@ def int4_group(name: str, N: int, K: int, group: int = INT4_GROUP) -> int:
         raise ValueError(f"{name} {(N, K)}: int4 weights need both dimensions to be multiples of 64 and a group "
                          f"size ({G}) that is a multiple of 64 and divides K")
     return G
+
+
+def quantize_experts_int4(w: torch.Tensor, name: str = "experts"):
+    """(codes uint8 [E, N, K / 2], s f32 [E, N, K / G], z uint8 [E, N, K / G]) of a stacked expert weight:
+    ops.reference.quantize_weight_int4 over its E N rows with the group size of int4_group."""
+    E, N, K = w.shape
+    G = int4_group(name, N, K)
+    codes, s, z = ref.quantize_weight_int4(w.reshape(E * N, K), G)
+    return codes.view(E, N, K // 2), s.view(E, N, K // G), z.view(E, N, K // G)
 
 
 def mxfp4_check(name: str, N: int, K: int) -> None:
@@ -283,7 +292,7 @@ def tp_kv_heads(num_kv_heads: int, world: int) -> int:
 
 class LlamaLayer:
     def __init__(self, cfg: LlamaConfig, tp: TPInfo, device, dtype, fp8: bool = False, int4: bool = False,
-                 name: str = "layers.?", experts_fp8: bool = False, mxfp4: bool = False):
+                 name: str = "layers.?", experts_fp8: bool = False, mxfp4: bool = False, experts_int4: bool = False):
         H, D = cfg.hidden_size, cfg.head_dim
         assert cfg.num_heads % tp.world == 0, "TP must divide the query heads"
         assert cfg.intermediate_size % tp.world == 0
@@ -298,7 +307,7 @@ class LlamaLayer:
         # of gate_up_w / down_w: gate_up [E, 2F, H] (an expert's gate rows, then its up rows)
         self.moe = cfg.num_experts > 0
         self.gate_up_w = self.down_w = self.router_w = self.experts_gate_up_w = self.experts_down_w = None
-        self.experts_gate_up_s = self.experts_down_s = None
+        self.experts_gate_up_s = self.experts_down_s = self.experts_gate_up_z = self.experts_down_z = None
         if self.moe:
             E, Fm = cfg.num_experts, cfg.moe_intermediate_size
             self.router_w = mk(E, H)
@@ -310,6 +319,12 @@ class LlamaLayer:
                     codes, sc = quantize_experts_fp8(getattr(self, n + "_w"))
                     setattr(self, n + "_w", codes)
                     setattr(self, n + "_s", sc)
+            # int4 experts: packed codes [E, N, K / 2] + f32 scale and uint8 zero point per (expert, output
+            # row, group of input columns), the dense int4 format per expert, likewise
+            if experts_int4:
+                for n in EXPERT_NAMES:
+                    for suffix, t in zip(("_w", "_s", "_z"), quantize_experts_int4(getattr(self, n + "_w"), f"{name}.{n}_w")):
+                        setattr(self, n + suffix, t)
         else:
             self.gate_up_w = mk(2 * self.f, H)
             self.down_w = mk(H, self.f) / math.sqrt(2 * cfg.num_layers)
@@ -352,6 +367,8 @@ class LlamaLayer:
         t = [self.qkv_w, self.o_w, *mlp, self.in_norm, self.post_norm]
         if self.experts_gate_up_s is not None:
             t += [self.experts_gate_up_s, self.experts_down_s]
+        if self.experts_gate_up_z is not None:
+            t += [self.experts_gate_up_z, self.experts_down_z]
         if self.qkv_s is not None:
             t += [self.qkv_s, self.o_s, self.gate_up_s, self.down_s]
         if self.qkv_z is not None:
@@ -375,9 +392,9 @@ class LlamaModel:
             raise ValueError(f"activations_dtype must be one of {ACTIVATIONS_DTYPES}, got {activations_dtype!r}")
         if experts_dtype not in EXPERTS_DTYPES:
             raise ValueError(f"experts_dtype must be one of {EXPERTS_DTYPES}, got {experts_dtype!r}")
-        if experts_dtype == "fp8" and not cfg.num_experts:
-            raise ValueError(f"experts_dtype='fp8' on a dense model ({cfg.name}): it has no experts; "
-                             f"weights_dtype='fp8' quantises its projections")
+        if experts_dtype != "bf16" and not cfg.num_experts:
+            raise ValueError(f"experts_dtype={experts_dtype!r} on a dense model ({cfg.name}): it has no experts; "
+                             f"weights_dtype={experts_dtype!r} quantises its projections")
         if weights_dtype == "mxfp4":
             # refused by name, with the reason
             if activations_dtype == "fp8":
@@ -393,7 +410,7 @@ class LlamaModel:
             # refused by name, never silently served
             if weights_dtype != "bf16" or activations_dtype != "bf16":
                 raise ValueError(f"a mixture-of-experts model ({cfg.name}) with fp8 or int4 weights or fp8 activations "
-                                 f"is not supported, with or without experts_dtype='fp8': only the expert matrices "
+                                 f"is not supported, with or without experts_dtype='fp8' or 'int4': only the expert matrices "
                                  f"have a quantised form (experts_dtype), the other projections stay bf16")
             if tp is not None and tp.world > 1:
                 raise ValueError(f"a mixture-of-experts model ({cfg.name}) under tensor parallelism (world "
@@ -418,7 +435,9 @@ class LlamaModel:
         self.weights_dtype = weights_dtype
         # "fp8": the two stacked expert matrices of every mixture-of-experts layer are float8_e4m3fn
         # codes with one f32 scale per (expert, output row) and the grouped GEMMs run W8A16
-        # (ops/csrc/moe.hip); the router and every other tensor keep their type and their route
+        # (ops/csrc/moe.hip); "int4": they are packed 4-bit codes with an f32 scale and a zero point per
+        # (expert, output row, group of input columns) and the grouped GEMMs run W4A16 (moe_gemm_w4);
+        # the router and every other tensor keep their type and their route
         self.experts_dtype = experts_dtype
         self.cfg = cfg
         self.device = torch.device(device)
@@ -434,7 +453,8 @@ class LlamaModel:
             self.embed = (torch.randn(self.vocab_per_rank, H, device=self.device) * 0.02).to(dtype)
             self.layers = [LlamaLayer(cfg, self.tp, self.device, dtype, fp8=weights_dtype == "fp8",
                                       int4=weights_dtype == "int4", name=f"layers.{i}",
-                                      experts_fp8=experts_dtype == "fp8", mxfp4=weights_dtype == "mxfp4")
+                                      experts_fp8=experts_dtype == "fp8", mxfp4=weights_dtype == "mxfp4",
+                                      experts_int4=experts_dtype == "int4")
                            for i in range(cfg.num_layers)]
             self.final_norm = torch.ones(H, device=self.device, dtype=dtype)
             self.lm_head = self.embed if cfg.tie_embeddings else (
@@ -472,8 +492,10 @@ class LlamaModel:
             names += ("qkv_b",)
         if self.cfg.qk_norm:
             names += ("q_norm", "k_norm")
-        if self.experts_dtype == "fp8":
+        if self.experts_dtype in ("fp8", "int4"):
             names += tuple(n + "_s" for n in EXPERT_NAMES)
+        if self.experts_dtype == "int4":
+            names += tuple(n + "_z" for n in EXPERT_NAMES)
         if self.weights_dtype in ("fp8", "int4", "mxfp4"):
             names += tuple(n + "_s" for n in W8_NAMES)
         if self.weights_dtype == "int4":
@@ -503,7 +525,7 @@ class LlamaModel:
                 if n[:-2] in EXPERT_NAMES:
                     if n.endswith("_w"):
                         self._load_experts(l, n[:-2], key, sd)
-                    continue   # a scale: loaded with its weight
+                    continue   # a scale or a zero point: loaded with its weight
                 src = sd[key]
                 if n.endswith("_w") and n[:-2] in W8_NAMES:
                     zkey = f"layers.{i}.{n[:-2]}_z"
@@ -542,8 +564,39 @@ class LlamaModel:
 
     def _load_experts(self, layer: LlamaLayer, n: str, key: str, sd: dict) -> None:
         """One stacked expert matrix: as it is for bf16 experts; for fp8 experts the (codes, scale)
-        pair of the state dict, or a wider tensor quantised here with the one rule."""
-        src, skey, dst = sd[key], key[:-2] + "_s", getattr(layer, n + "_w")
+        pair of the state dict, for int4 experts the (codes, scale, zero) triple as it is (its group
+        size may differ from the one the model was built with), or a wider tensor quantised here
+        with the one rule."""
+        src, skey, zkey, dst = sd[key], key[:-2] + "_s", key[:-2] + "_z", getattr(layer, n + "_w")
+        if self.experts_dtype != "int4" and (src.dtype == torch.uint8 or zkey in sd):
+            raise ValueError(f"{key} holds int4 codes but the model's experts_dtype is {self.experts_dtype!r}; build "
+                             f"the model with experts_dtype='int4'")
+        if self.experts_dtype == "int4":
+            E, N, K = dst.shape[0], dst.shape[1], 2 * dst.shape[2]
+            if ref.is_fp8(src):
+                raise ValueError(f"{key} holds float8_e4m3fn codes but the model's experts_dtype is 'int4'")
+            if src.dtype == torch.uint8:
+                for mk in (skey, zkey):
+                    if mk not in sd:
+                        raise ValueError(f"{key} holds int4 codes but {mk} is missing")
+                if tuple(src.shape) != (E, N, K // 2):
+                    raise ValueError(f"{key} has shape {tuple(src.shape)}, expected packed codes {(E, N, K // 2)}")
+                sc, zp = sd[skey].to(torch.float32), sd[zkey]
+                if sc.dim() != 3 or tuple(sc.shape[:2]) != (E, N) or zp.shape != sc.shape or zp.dtype != torch.uint8:
+                    raise ValueError(f"{skey} / {zkey} must be f32 and uint8 [{E}, {N}, K / G], got "
+                                     f"{tuple(sc.shape)} and {tuple(zp.shape)} {zp.dtype}")
+                int4_group(key, N, K, K // sc.shape[2] if sc.shape[2] and K % sc.shape[2] == 0 else 1)
+                t = (src, sc, zp)
+            elif skey in sd or zkey in sd:
+                raise ValueError(f"{skey} or {zkey} is present but {key} holds {src.dtype}, not int4 codes")
+            else:   # a wider tensor: quantise it with the one rule
+                if tuple(src.shape) != (E, N, K):
+                    raise ValueError(f"{key} has shape {tuple(src.shape)}, expected {(E, N, K)}")
+                t = quantize_experts_int4(src.to(self.device), key)
+            for suffix, v in zip(("_w", "_s", "_z"), t):
+                setattr(layer, n + suffix, v.to(self.device).contiguous())
+            self._runner = None
+            return
         if self.experts_dtype != "fp8":
             if ref.is_fp8(src) or skey in sd:
                 raise ValueError(f"{key} holds float8_e4m3fn codes but the model's experts_dtype is 'bf16'; build "
@@ -666,7 +719,8 @@ class LlamaModel:
             if layer.moe:
                 d = ops.moe_mlp(o, layer.router_w, layer.experts_gate_up_w, layer.experts_down_w,
                                 cfg.experts_per_token, cfg.norm_topk_prob, gate_up_s=layer.experts_gate_up_s,
-                                down_s=layer.experts_down_s)
+                                down_s=layer.experts_down_s, gate_up_z=layer.experts_gate_up_z,
+                                down_z=layer.experts_down_z)
                 a = None
             elif layer.gate_up_s is not None:
                 gu = _linear(o, layer.gate_up_w, layer.gate_up_s, a8, layer.gate_up_z)
@@ -721,7 +775,9 @@ class LlamaModel:
             **(dict(router_w=[l.router_w for l in L], experts_gate_up_w=[l.experts_gate_up_w for l in L],
                     experts_down_w=[l.experts_down_w for l in L], experts_per_token=self.cfg.experts_per_token,
                     norm_topk=self.cfg.norm_topk_prob) if moe else {}),
-            **({n + "_s": [getattr(l, n + "_s") for l in L] for n in EXPERT_NAMES} if self.experts_dtype == "fp8" else {}))
+            **({n + "_s": [getattr(l, n + "_s") for l in L] for n in EXPERT_NAMES}
+               if self.experts_dtype in ("fp8", "int4") else {}),
+            **({n + "_z": [getattr(l, n + "_z") for l in L] for n in EXPERT_NAMES} if self.experts_dtype == "int4" else {}))
         self._runner = (key, runner, kv_caches)
         return runner
 

@@ -327,7 +327,7 @@ def moe_route(x, router_w, k: int, norm_topk: bool):
 
 
 def moe_mlp(x, router_w, gate_up_w, down_w, k: int, norm_topk: bool, out=None, route=None, tile_rows: int = 0,
-            gate_up_s=None, down_s=None):
+            gate_up_s=None, down_s=None, gate_up_z=None, down_z=None):
     """Sparse MoE MLP: out[t] = sum over the k routed experts e of topk_w * down_w[e] .
     (silu(gate_w[e] . x_t) * (up_w[e] . x_t)), with gate_up_w [E, 2F, H] and down_w [E, H, F]
     (ops/csrc/moe.hip: route, align, two grouped GEMMs, combine; rounding points in
@@ -335,23 +335,48 @@ def moe_mlp(x, router_w, gate_up_w, down_w, k: int, norm_topk: bool, out=None, r
     ``tile_rows`` 32 or 128 forces the row-tile height of the grouped GEMMs (0: the rule).
     With ``gate_up_s`` f32 [E, 2F] and ``down_s`` f32 [E, H] the expert weights are
     float8_e4m3fn codes with one scale per (expert, output row) and the grouped GEMMs run
-    W8A16: the scale multiplies the f32 sum once."""
-    _moe_check(x, router_w, k, down_w.shape[2])
+    W8A16: the scale multiplies the f32 sum once.  With the zero points ``gate_up_z`` /
+    ``down_z`` as well the expert weights are packed int4 codes uint8 [E, 2F, H / 2] and
+    [E, H, F / 2] (ops.reference.pack_weight_int4 per expert) with f32 scales and uint8 zero
+    points [E, rows, K / G] per group of G input columns, and the grouped GEMMs run W4A16: the
+    scale multiplies each group's f32 partial sum of x * (q - z) once."""
+    w4 = gate_up_z is not None
+    if w4 != (down_z is not None):
+        raise ValueError("moe_mlp: gate_up_z and down_z are given together or not at all")
+    if not w4 and (gate_up_w.dtype == torch.uint8 or down_w.dtype == torch.uint8):
+        raise ValueError("moe_mlp: the expert weights hold uint8 int4 codes but no scales and zero points (gate_up_s, "
+                         "gate_up_z, down_s, down_z) were given")
+    _moe_check(x, router_w, k, (2 if w4 else 1) * down_w.shape[2])
     if (gate_up_s is None) != (down_s is None):
         raise ValueError("moe_mlp: gate_up_s and down_s are given together or not at all")
+    if w4 and gate_up_s is None:
+        raise ValueError("moe_mlp: the zero points gate_up_z / down_z need the scales gate_up_s / down_s")
     if gate_up_s is None and (ref.is_fp8(gate_up_w) or ref.is_fp8(down_w)):
         raise ValueError("moe_mlp: the expert weights hold float8_e4m3fn codes but gate_up_s / down_s were not given")
     if _gpu(x, gate_up_w, down_w):
         ids, w = route if route is not None else moe_route(x, router_w, k, norm_topk)
         out = torch.empty_like(x) if out is None else out
-        hip().moe_experts(out, x, gate_up_w, down_w, ids, w, tile_rows, gate_up_s, down_s)
+        hip().moe_experts(out, x, gate_up_w, down_w, ids, w, tile_rows, gate_up_s, down_s, gate_up_z, down_z)
         return out
-    if gate_up_s is not None:
+    if w4:
+        E, F2, H = gate_up_w.shape[0], gate_up_w.shape[1], 2 * gate_up_w.shape[2]
+        if gate_up_w.dtype != torch.uint8 or down_w.dtype != torch.uint8:
+            raise ValueError(f"moe_mlp: with gate_up_z / down_z the expert weights must be uint8 int4 codes, got "
+                             f"{gate_up_w.dtype} and {down_w.dtype}")
+        for name, s, z, rows, K in (("gate_up", gate_up_s, gate_up_z, F2, H), ("down", down_s, down_z, H, F2 // 2)):
+            NG = s.shape[2] if s.dim() == 3 else 0
+            if s.dtype != torch.float32 or tuple(s.shape[:2]) != (E, rows) or NG < 1 or K % NG or (K // NG) % 64:
+                raise ValueError(f"moe_mlp: {name}_s must be float32 [{E}, {rows}, K / G] with a group size G that is a "
+                                 f"multiple of 64 and divides K = {K}, got {s.dtype} {tuple(s.shape)}")
+            if z.dtype != torch.uint8 or z.shape != s.shape:
+                raise ValueError(f"moe_mlp: {name}_z must be uint8 {tuple(s.shape)}, got {z.dtype} {tuple(z.shape)}")
+    elif gate_up_s is not None:
         E, F2, H = gate_up_w.shape
         for name, s, shape in (("gate_up_s", gate_up_s, (E, F2)), ("down_s", down_s, (E, H))):
             if s.dtype != torch.float32 or tuple(s.shape) != shape:
                 raise ValueError(f"moe_mlp: {name} must be float32 {shape}, got {s.dtype} {tuple(s.shape)}")
-    r = ref.moe_mlp(x, router_w, gate_up_w, down_w, k, norm_topk, route=route, gate_up_s=gate_up_s, down_s=down_s)
+    r = ref.moe_mlp(x, router_w, gate_up_w, down_w, k, norm_topk, route=route, gate_up_s=gate_up_s, down_s=down_s,
+                    gate_up_z=gate_up_z, down_z=down_z)
     if out is not None:
         out.copy_(r)
         return out
@@ -361,7 +386,8 @@ def moe_mlp(x, router_w, gate_up_w, down_w, k: int, norm_topk: bool, out=None, r
 def moe_launch_counts(reset: bool = False) -> dict:
     """Launches of the MoE kernels since the last reset: "route_mfma" / "route_dot",
     "align", "gate_up_bm32" / "gate_up_bm128", "down_bm32" / "down_bm128" (the row-tile
-    height of the grouped GEMMs; "gate_up_w8_bm32" ... "down_w8_bm128" with fp8 experts), "combine"."""
+    height of the grouped GEMMs; "gate_up_w8_bm32" ... "down_w8_bm128" with fp8 experts,
+    "gate_up_w4_bm32" ... "down_w4_bm128" with int4 experts), "combine"."""
     return dict(hip().moe_launch_counts(reset))
 
 

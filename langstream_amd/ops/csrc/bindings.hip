@@ -123,7 +123,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_route", &moe_route);
   m.def("moe_experts", &moe_experts, py::arg("out"), py::arg("x"), py::arg("gate_up_w"), py::arg("down_w"),
         py::arg("ids"), py::arg("wts"), py::arg("tile_rows") = 0, py::arg("gate_up_s") = py::none(),
-        py::arg("down_s") = py::none());
+        py::arg("down_s") = py::none(), py::arg("gate_up_z") = py::none(), py::arg("down_z") = py::none());
   m.def("moe_launch_counts", &moe_launch_counts, py::arg("reset") = false);
   bind_runners(m);
 }

@@ -126,6 +126,19 @@ __device__ __forceinline__ bf16x8 fp8_unpack8(uint2 w) {
   return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
 
+// int4 weights (gemm_w4.hip, moe.hip; layout in ops/reference.py pack_weight_int4):
+// 8 codes of one word -> bf16x8 of q - z (z as a float), element i = code i; exact
+__device__ __forceinline__ bf16x8 w4_unpack8(uint32_t v, float zf) {
+  const uint32_t lo = v & 0x0F0F0F0Fu, hi = (v >> 4) & 0x0F0F0F0Fu;
+  bf16x8 r;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    r[b] = (bf16)((float)((lo >> (8 * b)) & 0xffu) - zf);
+    r[b + 4] = (bf16)((float)((hi >> (8 * b)) & 0xffu) - zf);
+  }
+  return r;
+}
+
 // XCD-aware bijective remap of a linear workgroup id (guide §5 "XCD swizzle
 // must be bijective"): consecutive logical tiles land on the same XCD so they
 // share that XCD's L2.  Speed only -- never relied on for correctness.

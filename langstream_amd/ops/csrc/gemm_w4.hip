@@ -54,18 +54,6 @@ constexpr int BN = 64, BK = 64;
 constexpr int LDX = BK + 8;   // x LDS row, bf16 elements (144 B)
 constexpr int LDW = 48;       // w LDS row, bytes (32 B of codes + 16: 16-B stores stay aligned)
 
-// 8 codes of one word -> bf16x8 of q - z (z as a float), element i = code i; exact
-__device__ __forceinline__ bf16x8 w4_unpack8(uint32_t v, float zf) {
-  const uint32_t lo = v & 0x0F0F0F0Fu, hi = (v >> 4) & 0x0F0F0F0Fu;
-  bf16x8 r;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    r[b] = (bf16)((float)((lo >> (8 * b)) & 0xffu) - zf);
-    r[b + 4] = (bf16)((float)((hi >> (8 * b)) & 0xffu) - zf);
-  }
-  return r;
-}
-
 template <int BM, bool PARTIAL>
 __global__ void __launch_bounds__(256) w4_gemm_kernel(const bf16* __restrict__ x, int64_t ldx,
                                                       const uint8_t* __restrict__ w, const float* __restrict__ sc,

@@ -49,6 +49,19 @@
 //   T = 16 (profiles/moe_fp8/README.md): 143 us against 186 us with a 64-code step on the
 //   Qwen3-30B-A3B shape, 347 against 510 us on the Mixtral shape.  BM = 128 is compute-bound and
 //   keeps 64: two stages of its A tile and a 128-code weight tile would not fit in 64 KB.
+// moe_gemm_w4 the same grouped GEMM over int4 expert weights, the format of gemm_w4.hip per expert (W4A16):
+//   packed 4-bit codes, one f32 scale and one zero point per (expert, weight row, group of G input
+//   columns), y = sum_g s_g * sum_{k in g} a_k (q_k - z_g).  q - z is exact in bf16, so the products run
+//   on the bf16 MFMA into a per-group f32 partial that is folded into the accumulator with s_g where
+//   the group ends: the scales are in the main loop, not only in the epilogue.  BM = 32 keeps the
+//   weights nibbles from HBM to LDS and expands them at the MFMA operand (w4_unpack8), as the fp8
+//   form does with bytes; BM = 128, where all four waves need every weight row, expands a 16-B chunk
+//   once, in the thread that carries it, and stores bf16 of q - z in the bf16 kernel's LDS layout.
+//   K STEP: BM = 32 steps K by 256 codes, the byte count of the fp8 form's 128-code step (four or two
+//   16-B weight loads per thread in flight); its two stages take 69 KB (gate_up) of the 160 KB of LDS.
+//   Measured at T = 16 against a 128-code step (profiles/moe_int4/README.md): 212 against 225 us on the
+//   Qwen3-30B-A3B shape, 562 against 556 us on the Mixtral shape; the 128-code build was dropped.
+//   BM = 128 steps by 64 with two stages (72 KB in gate_up mode).
 // moe_combine out[t] = bf16(sum_s y[t, s]) with 16-B loads.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -527,6 +540,245 @@ __global__ void __launch_bounds__(256) moe_gemm_w8_kernel(const bf16* __restrict
     }
 }
 
+// ---------------------------------------------------------------------------- moe_gemm_w4
+// The grouped GEMM over int4 expert weights (W4A16): w holds packed 4-bit codes (two per byte, the
+// word order of w4_unpack8), sc one f32 scale and zp one zero point per (expert, weight row, group
+// of G input columns) -- [E, 2 N, K / G] in gate_up mode, [E, N, K / G] in down mode; G % 64 == 0.
+// Schedule, gather, scatter, tile heights and grid are those of moe_gemm_kernel; A stays bf16 in
+// LDS.  The MFMAs of a 64-code block accumulate into a per-group partial (gate and up each) that
+// is folded into the main f32 accumulator with the lane's scale where the group ends.  A lane's
+// scales (and, BM = 32, zero points) are fetched with the loads of the step in which a group
+// begins and staged in registers one step ahead, per 64-code block of the step.
+//   BM = 32: the weight tile stays nibbles from HBM to LDS (rows of BKW / 2 + 16 bytes); a lane
+//     expands the 8 codes of an MFMA operand from one 4-B LDS read with its column's zero point.
+//     A step may span several groups; a K that is no multiple of the step ends in a partial
+//     step whose upper chunks are zeros and read nothing, and whose empty blocks are skipped.
+//   BM = 128: the thread that carries a 16-B chunk (32 codes, inside one group) fetches the row's
+//     zero point with it and expands it to 32 bf16 of q - z on the way into LDS, so the weight tile
+//     has the bf16 kernel's layout and every code is decoded once, not once per wave.
+template <int BM, bool DOWN>
+__global__ void __launch_bounds__(256) moe_gemm_w4_kernel(const bf16* __restrict__ a, int64_t lda,
+                                                          const uint8_t* __restrict__ w, const float* __restrict__ sc,
+                                                          const uint8_t* __restrict__ zp,
+                                                          const int* __restrict__ num_tiles,
+                                                          const int* __restrict__ tile_expert,
+                                                          const int* __restrict__ sorted_rows,
+                                                          const float* __restrict__ topk_w, int kk, int K, int N, int G,
+                                                          bf16* __restrict__ out) {
+  constexpr bool EXP = BM == 128;                   // expand once per workgroup: W is bf16 of q - z in LDS
+  constexpr int BKW = BM == 32 ? 256 : 64;          // K step in codes (file header: moe_gemm_w4, K STEP)
+  constexpr int NH = BKW / 64;                      // 64-code blocks per step: a block lies inside one group
+  constexpr int NW = DOWN ? BN : 2 * BN;            // weight rows per K step
+  constexpr int LDA = BKW + 8;                      // A LDS row, bf16 elements
+  constexpr int LDW = EXP ? LDA * 2 : BKW / 2 + 16; // W LDS row, bytes (bf16 of q - z, or nibbles + pad)
+  constexpr int AS = BM * LDA * 2, WS = NW * LDW, STAGE = AS + WS;
+  constexpr int ACR = BKW / 8, WCR = BKW / 32;      // 16-B chunks per A row (8 bf16) and per W row (32 codes)
+  constexpr int AC = BM * ACR / 256;                // A chunks per thread per K step
+  constexpr int WCH = NW * WCR, WC = (WCH + 255) / 256;   // W chunks per step, per thread (BM = 128 down: threads < 128)
+  constexpr int WAVES_M = BM == 128 ? 4 : 1, WAVES_N = 4 / WAVES_M;
+  constexpr int IT = BM / WAVES_M / 16, JT = BN / WAVES_N / 16;
+  constexpr int U = DOWN ? 1 : 2;                   // gate only, or gate and up
+  static_assert(BM == 32 || BM == 128, "tile heights");
+  static_assert(2 * STAGE + 4 * BM <= 160 * 1024, "two LDS stages");
+  __shared__ __attribute__((aligned(16))) char lds[2 * STAGE];
+  __shared__ int srow[BM];
+  const int tile = blockIdx.y;
+  if (tile >= *num_tiles) return;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int e = tile_expert[tile];
+  const int n0 = blockIdx.x * BN;
+  const int NG = K / G;
+  const int64_t prow0 = (int64_t)tile * BM;
+  if (tid < BM) srow[tid] = sorted_rows[prow0 + tid];
+  __syncthreads();
+
+  const bf16* ap[AC];
+  bool aok[AC];
+#pragma unroll
+  for (int i = 0; i < AC; ++i) {
+    const int q = tid + 256 * i, row = q / ACR, c = q % ACR;
+    const int idx = srow[row];
+    aok[i] = idx >= 0;
+    const int64_t grow = DOWN ? prow0 + row : (aok[i] ? idx / kk : 0);
+    ap[i] = a + grow * lda + c * 8;
+  }
+  const int64_t erow0 = (int64_t)e * (DOWN ? N : 2 * N);   // the expert's first row in w, sc and zp
+  const uint8_t* wp[WC];
+  const uint8_t* zc[WC];   // BM = 128: the zero points of the chunk's row
+  bool wok[WC];
+#pragma unroll
+  for (int i = 0; i < WC; ++i) {
+    const int q = tid + 256 * i, row = q / WCR, c = q % WCR;
+    wok[i] = q < WCH;
+    const int grow = !wok[i] ? n0 : DOWN || row < BN ? n0 + row : N + n0 + row - BN;   // gate rows, then the matching up rows
+    wp[i] = w + (erow0 + grow) * (K / 2) + c * 16;
+    zc[i] = zp + (erow0 + grow) * NG;
+  }
+  const int rb = (BM == 128 ? wid : 0) * (BM / WAVES_M);    // first tile row of this wave
+  const int cb = (BM == 128 ? 0 : wid) * (BN / WAVES_N);    // first tile column of this wave
+  const int fr = lane & 15, fq = lane >> 4, fk = 8 * fq;
+  // this lane's output columns are n0 + cb + 16 j + fr: gate row n, up row N + n of the expert
+  const float* sp[JT][U];
+  const uint8_t* zq[JT][U];
+#pragma unroll
+  for (int j = 0; j < JT; ++j)
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t row = erow0 + u * N + n0 + cb + 16 * j + fr;
+      sp[j][u] = sc + row * NG;
+      zq[j][u] = zp + row * NG;
+    }
+  uint4 ra[AC], rw[WC];
+  float rzc[WC];                             // BM = 128: zero point of the chunk in rw
+  float rs[NH][JT][U], rz[NH][JT][U];        // fetched: per block of the step last loaded
+  float cs[NH][JT][U], cz[NH][JT][U];        // staged: per block of the step in LDS
+#pragma unroll
+  for (int h = 0; h < NH; ++h)
+#pragma unroll
+    for (int j = 0; j < JT; ++j)
+#pragma unroll
+      for (int u = 0; u < U; ++u) rs[h][j][u] = rz[h][j][u] = 0.f;
+  auto gload = [&](int kt) {
+    const int ko = kt * BKW;
+#pragma unroll
+    for (int i = 0; i < AC; ++i) {
+      const bool in = NH == 1 || ko + ((tid + 256 * i) % ACR) * 8 < K;   // false past K in a partial step
+      ra[i] = aok[i] && in ? ld16(ap[i] + ko) : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < WC; ++i) {
+      const int kc = ko + ((tid + 256 * i) % WCR) * 32;
+      const bool in = wok[i] && (NH == 1 || kc < K);
+      rw[i] = !in ? make_uint4(0, 0, 0, 0) : BM == 32 ? ld16_nt(wp[i] + ko / 2) : ld16(wp[i] + ko / 2);
+      if constexpr (EXP) rzc[i] = in ? (float)zc[i][kc / G] : 0.f;
+    }
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const int k = ko + 64 * h;
+      const bool begins = k < K && k % G == 0;   // wave-uniform
+      const int g = k / G;
+#pragma unroll
+      for (int j = 0; j < JT; ++j)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          // a block inside a group inherits from the block before it (the last one of the previous step)
+          const int hp = h == 0 ? NH - 1 : h - 1;
+          rs[h][j][u] = begins ? sp[j][u][g] : rs[hp][j][u];
+          if constexpr (!EXP) rz[h][j][u] = begins ? (float)zq[j][u][g] : rz[hp][j][u];
+        }
+    }
+  };
+  auto lstore = [&](int buf) {
+    char* la = lds + buf * STAGE;
+    char* lw = la + AS;
+#pragma unroll
+    for (int i = 0; i < AC; ++i) {
+      const int q = tid + 256 * i;
+      st16(la + ((q / ACR) * LDA + (q % ACR) * 8) * 2, ra[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < WC; ++i) {
+      const int q = tid + 256 * i;
+      if (!wok[i]) continue;
+      if constexpr (EXP) {
+        const uint32_t words[4] = {rw[i].x, rw[i].y, rw[i].z, rw[i].w};
+#pragma unroll
+        for (int v = 0; v < 4; ++v)   // word v holds codes 8 v .. 8 v + 7 of the chunk
+          st16(lw + (q / WCR) * LDW + ((q % WCR) * 32 + 8 * v) * 2,
+               __builtin_bit_cast(uint4, w4_unpack8(words[v], rzc[i])));
+      } else {
+        st16(lw + (q / WCR) * LDW + (q % WCR) * 16, rw[i]);
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < NH; ++h)
+#pragma unroll
+      for (int j = 0; j < JT; ++j)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          cs[h][j][u] = rs[h][j][u];
+          cz[h][j][u] = rz[h][j][u];
+        }
+  };
+
+  f32x4 acc[IT][JT][U], grp[IT][JT][U];
+#pragma unroll
+  for (int i = 0; i < IT; ++i)
+#pragma unroll
+    for (int j = 0; j < JT; ++j)
+#pragma unroll
+      for (int u = 0; u < U; ++u) acc[i][j][u] = grp[i][j][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int nk = (K + BKW - 1) / BKW;
+  gload(0);
+  lstore(0);
+  if (nk > 1) gload(1);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const char* la = lds + (kt & 1) * STAGE;
+    const char* lw = la + AS;
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const int k = kt * BKW + 64 * h;
+      if (NH > 1 && k >= K) continue;   // an empty block of the partial last step (wave-uniform)
+#pragma unroll
+      for (int ks = 2 * h; ks < 2 * h + 2; ++ks) {
+        bf16x8 av[IT];
+#pragma unroll
+        for (int i = 0; i < IT; ++i) av[i] = lds8(la + ((rb + 16 * i + fr) * LDA + 32 * ks + fk) * 2);
+#pragma unroll
+        for (int j = 0; j < JT; ++j)
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            const char* wrow = lw + (u * BN + cb + 16 * j + fr) * LDW;
+            bf16x8 b;
+            if constexpr (EXP) b = lds8(wrow + (32 * ks + fk) * 2);
+            else b = w4_unpack8(*reinterpret_cast<const uint32_t*>(wrow + 16 * ks + 4 * fq), cz[h][j][u]);
+#pragma unroll
+            for (int i = 0; i < IT; ++i)
+              grp[i][j][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i], b, grp[i][j][u], 0, 0, 0);
+          }
+      }
+      // the group ends with this block (K % G == 0: the last block ends one): fold its partial in with the scale
+      if ((k + 64) % G == 0) {
+#pragma unroll
+        for (int i = 0; i < IT; ++i)
+#pragma unroll
+          for (int j = 0; j < JT; ++j)
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) acc[i][j][u][r] = fmaf(grp[i][j][u][r], cs[h][j][u], acc[i][j][u][r]);
+              grp[i][j][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+      }
+    }
+    if (kt + 1 < nk) {
+      lstore((kt + 1) & 1);
+      if (kt + 2 < nk) gload(kt + 2);
+    }
+    __syncthreads();
+  }
+
+  // acc[i][j][u][r] = C[rb + 16 i + 4 (lane >> 4) + r][cb + 16 j + fr] (tile-local), u = 1: the up half
+#pragma unroll
+  for (int i = 0; i < IT; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = rb + 16 * i + 4 * fq + r;
+      const int idx = srow[row];
+      if (idx < 0) continue;   // padding row
+      const float tw = DOWN ? topk_w[idx] : 0.f;
+      bf16* orow = out + (DOWN ? (int64_t)idx : prow0 + row) * N + n0 + cb + fr;
+#pragma unroll
+      for (int j = 0; j < JT; ++j) {
+        const float g = acc[i][j][0][r];
+        if constexpr (DOWN) orow[16 * j] = (bf16)(tw * g);
+        else orow[16 * j] = (bf16)(g / (1.f + expf(-g)) * acc[i][j][U - 1][r]);
+      }
+    }
+}
+
 // ---------------------------------------------------------------------------- moe_combine
 // One thread per 16-B chunk of out.
 __global__ void __launch_bounds__(256) moe_combine_kernel(const bf16* __restrict__ y, const int* __restrict__ ids,
@@ -551,6 +803,7 @@ __global__ void __launch_bounds__(256) moe_combine_kernel(const bf16* __restrict
 // Host-side launch census (moe_launch_counts), relaxed atomics on the host only.
 std::atomic<int64_t> g_route[2], g_align, g_gemm[2][2], g_combine;   // route [mfma]; gemm [BM == 128][down]
 std::atomic<int64_t> g_gemm_w8[2][2];                                // the fp8-code GEMMs, likewise
+std::atomic<int64_t> g_gemm_w4[2][2];                                // the int4-code GEMMs, likewise
 
 bool aligned16(const at::Tensor& t) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0; }
 
@@ -600,6 +853,60 @@ void gemm_w8_launch(hipStream_t st, const at::Tensor& x, const at::Tensor& gate_
       y);
 }
 
+// The same two launches over int4 codes, their group scales and zero points; the group sizes
+// are read from the scales' last dimension.
+template <int BM>
+void gemm_w4_launch(hipStream_t st, const at::Tensor& x, const at::Tensor& gate_up_w, const at::Tensor& down_w,
+                    const at::Tensor& gate_up_s, const at::Tensor& down_s, const at::Tensor& gate_up_z,
+                    const at::Tensor& down_z, const int* meta, int64_t max_tiles, const float* wts, int k, bf16* act,
+                    bf16* y) {
+  const int H = (int)x.size(1), F = (int)(2 * down_w.size(2));
+  const int* tile_expert = meta + 1;
+  const int* sorted_rows = meta + 1 + max_tiles;
+  g_gemm_w4[BM == 128][0].fetch_add(1, std::memory_order_relaxed);
+  g_gemm_w4[BM == 128][1].fetch_add(1, std::memory_order_relaxed);
+  moe_gemm_w4_kernel<BM, false><<<dim3(F / BN, (unsigned)max_tiles), 256, 0, st>>>(
+      (const bf16*)x.data_ptr(), x.stride(0), gate_up_w.data_ptr<uint8_t>(), gate_up_s.data_ptr<float>(),
+      gate_up_z.data_ptr<uint8_t>(), meta, tile_expert, sorted_rows, nullptr, k, H, F, H / (int)gate_up_s.size(2), act);
+  moe_gemm_w4_kernel<BM, true><<<dim3(H / BN, (unsigned)max_tiles), 256, 0, st>>>(
+      act, F, down_w.data_ptr<uint8_t>(), down_s.data_ptr<float>(), down_z.data_ptr<uint8_t>(), meta, tile_expert,
+      sorted_rows, wts, k, F, H, F / (int)down_s.size(2), y);
+}
+
+// Every guard of the int4 form of moe_experts: codes uint8 [E, 2F, H / 2] and [E, H, F / 2], scales
+// f32 and zero points uint8 [E, rows, K / G].
+void check_w4_experts(const at::Tensor& gate_up_w, const at::Tensor& down_w, const at::Tensor& gate_up_s,
+                      const at::Tensor& down_s, const at::Tensor& gate_up_z, const at::Tensor& down_z) {
+  TORCH_CHECK(gate_up_w.scalar_type() == at::kByte && down_w.scalar_type() == at::kByte,
+              "moe_experts: with gate_up_z / down_z the expert weights must be uint8 int4 codes (two per byte), got ",
+              gate_up_w.scalar_type(), " and ", down_w.scalar_type());
+  TORCH_CHECK(gate_up_w.is_cuda() && down_w.is_cuda() && gate_up_w.dim() == 3 && down_w.dim() == 3 &&
+                  gate_up_w.is_contiguous() && down_w.is_contiguous() && aligned16(gate_up_w) && aligned16(down_w),
+              "moe_experts: int4 gate_up_w [E, 2F, H / 2] and down_w [E, H, F / 2] must be contiguous 16-byte aligned "
+              "uint8 on the GPU");
+  const int64_t E = gate_up_w.size(0), H = 2 * gate_up_w.size(2), F = 2 * down_w.size(2);
+  const at::Tensor* ss[2] = {&gate_up_s, &down_s};
+  const at::Tensor* zs[2] = {&gate_up_z, &down_z};
+  const char* names[2] = {"gate_up", "down"};
+  const int64_t rows[2] = {2 * F, H}, Ks[2] = {H, F};
+  for (int i = 0; i < 2; ++i) {
+    const at::Tensor &s = *ss[i], &z = *zs[i];
+    const char* n = names[i];
+    TORCH_CHECK(s.is_cuda() && z.is_cuda() && s.device() == gate_up_w.device() && z.device() == gate_up_w.device(),
+                "moe_experts: ", n, "_s and ", n, "_z must be on the device of the weights");
+    TORCH_CHECK(s.scalar_type() == at::kFloat, "moe_experts: ", n, "_s must be float32, got ", s.scalar_type());
+    TORCH_CHECK(z.scalar_type() == at::kByte, "moe_experts: ", n, "_z must be uint8, got ", z.scalar_type());
+    TORCH_CHECK(s.dim() == 3 && s.size(0) == E && s.size(1) == rows[i] && s.size(2) >= 1 && Ks[i] % s.size(2) == 0 &&
+                    (Ks[i] / s.size(2)) % 64 == 0,
+                "moe_experts: ", n, "_s has shape ", s.sizes(), ", expected [", E, ", ", rows[i],
+                ", K / G] with a group size G that is a multiple of 64 and divides K = ", Ks[i]);
+    TORCH_CHECK(z.sizes() == s.sizes(), "moe_experts: ", n, "_z has shape ", z.sizes(), ", expected the shape of ", n,
+                "_s ", s.sizes());
+    TORCH_CHECK(s.is_contiguous() && z.is_contiguous(), "moe_experts: ", n, "_s and ", n, "_z must be contiguous");
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(s.data_ptr()) & 3) == 0, "moe_experts: ", n, "_s must be 4-byte aligned");
+  }
+}
+
 }  // namespace
 
 // The shape rule of the MoE kernels.
@@ -640,25 +947,38 @@ void moe_route(at::Tensor ids, at::Tensor wts, at::Tensor x, at::Tensor router_w
 // out[t] = sum over the k slots of row t of topk_w * expert(x_t): moe_align, the two grouped
 // GEMMs and moe_combine.  tile_rows_force: 0 for the rule, else 32 or 128.  With the scales
 // gate_up_s f32 [E, 2F] and down_s f32 [E, H] (together or not at all) the weights are
-// float8_e4m3fn codes and the W8 kernels run; without them the weights are bf16.
+// float8_e4m3fn codes and the W8 kernels run; without them the weights are bf16.  With the zero
+// points gate_up_z / down_z as well (uint8, together or not at all, they need the scales) the
+// weights are packed int4 codes uint8 [E, 2F, H / 2] and [E, H, F / 2], scales and zero points
+// are [E, rows, K / G] per matrix, and the W4 kernels run.
 void moe_experts(at::Tensor out, at::Tensor x, at::Tensor gate_up_w, at::Tensor down_w, at::Tensor ids,
                  at::Tensor wts, int64_t tile_rows_force, c10::optional<at::Tensor> gate_up_s,
-                 c10::optional<at::Tensor> down_s) {
+                 c10::optional<at::Tensor> down_s, c10::optional<at::Tensor> gate_up_z,
+                 c10::optional<at::Tensor> down_z) {
   TORCH_CHECK(gate_up_s.has_value() == down_s.has_value(),
               "moe_experts: gate_up_s and down_s are given together or not at all");
-  const bool w8 = gate_up_s.has_value();
+  TORCH_CHECK(gate_up_z.has_value() == down_z.has_value(),
+              "moe_experts: gate_up_z and down_z are given together or not at all");
+  const bool w4 = gate_up_z.has_value();
+  TORCH_CHECK(!w4 || gate_up_s.has_value(),
+              "moe_experts: the zero points gate_up_z / down_z need the scales gate_up_s / down_s");
+  if (w4) check_w4_experts(gate_up_w, down_w, *gate_up_s, *down_s, *gate_up_z, *down_z);
+  const bool w8 = gate_up_s.has_value() && !w4;
   const auto wt = gate_up_w.scalar_type();
+  TORCH_CHECK(w4 || (wt != at::kByte && down_w.scalar_type() != at::kByte),
+              "moe_experts: the expert weights hold uint8 int4 codes but no scales and zero points (gate_up_s, "
+              "gate_up_z, down_s, down_z) were given");
   TORCH_CHECK(w8 || (wt != at::kFloat8_e4m3fn && down_w.scalar_type() != at::kFloat8_e4m3fn),
               "moe_experts: the expert weights hold float8_e4m3fn codes but no scales (gate_up_s, down_s) were given");
-  TORCH_CHECK(!w8 || (wt == at::kFloat8_e4m3fn && down_w.scalar_type() == at::kFloat8_e4m3fn),
+  TORCH_CHECK(w4 || !w8 || (wt == at::kFloat8_e4m3fn && down_w.scalar_type() == at::kFloat8_e4m3fn),
               "moe_experts: with gate_up_s / down_s the expert weights must be float8_e4m3fn codes, got ", wt, " and ",
               down_w.scalar_type());
-  TORCH_CHECK(gate_up_w.is_cuda() && down_w.is_cuda() && (w8 || wt == at::kBFloat16) &&
+  TORCH_CHECK(gate_up_w.is_cuda() && down_w.is_cuda() && (w8 || w4 || wt == at::kBFloat16) &&
                   down_w.scalar_type() == wt && gate_up_w.dim() == 3 && down_w.dim() == 3 &&
                   gate_up_w.is_contiguous() && down_w.is_contiguous() && aligned16(gate_up_w) && aligned16(down_w),
               "moe_experts: gate_up_w [E, 2F, H] and down_w [E, H, F] must be contiguous 16-byte aligned bf16 (with "
               "scales: float8_e4m3fn) on the GPU");
-  const int64_t E = gate_up_w.size(0), H = gate_up_w.size(2), F = down_w.size(2);
+  const int64_t E = gate_up_w.size(0), H = (w4 ? 2 : 1) * gate_up_w.size(2), F = (w4 ? 2 : 1) * down_w.size(2);
   TORCH_CHECK(gate_up_w.size(1) == 2 * F && down_w.size(0) == E && down_w.size(1) == H,
               "moe_experts: gate_up_w ", gate_up_w.sizes(), " and down_w ", down_w.sizes(),
               " are not [E, 2F, H] and [E, H, F]");
@@ -707,7 +1027,13 @@ void moe_experts(at::Tensor out, at::Tensor x, at::Tensor gate_up_w, at::Tensor 
   int* mp = meta.data_ptr<int>();
   g_align.fetch_add(1, std::memory_order_relaxed);
   moe_align_kernel<<<1, 1024, 0, st>>>(ids.data_ptr<int>(), (int)n, (int)E, BM, mp, mp + 1, mp + 1 + max_tiles);
-  if (w8 && BM == 32)
+  if (w4 && BM == 32)
+    gemm_w4_launch<32>(st, x, gate_up_w, down_w, *gate_up_s, *down_s, *gate_up_z, *down_z, mp, max_tiles,
+                       wts.data_ptr<float>(), (int)k, (bf16*)act.data_ptr(), (bf16*)y.data_ptr());
+  else if (w4)
+    gemm_w4_launch<128>(st, x, gate_up_w, down_w, *gate_up_s, *down_s, *gate_up_z, *down_z, mp, max_tiles,
+                        wts.data_ptr<float>(), (int)k, (bf16*)act.data_ptr(), (bf16*)y.data_ptr());
+  else if (w8 && BM == 32)
     gemm_w8_launch<32>(st, x, gate_up_w, down_w, *gate_up_s, *down_s, mp, max_tiles, wts.data_ptr<float>(), (int)k,
                        (bf16*)act.data_ptr(), (bf16*)y.data_ptr());
   else if (w8)
@@ -727,8 +1053,9 @@ void moe_experts(at::Tensor out, at::Tensor x, at::Tensor gate_up_w, at::Tensor 
 }
 
 // The launch census since the last reset: {"route_mfma": n, "route_dot": n, "align": n,
-// "gate_up_bm32": n, "down_bm128": n, "gate_up_w8_bm32": n, "down_w8_bm128": n, "combine": n} (keys
-// with a zero count are left out; the w8 keys count the fp8-code GEMMs).
+// "gate_up_bm32": n, "down_bm128": n, "gate_up_w8_bm32": n, "down_w8_bm128": n, "gate_up_w4_bm32": n,
+// "down_w4_bm128": n, "combine": n} (keys with a zero count are left out; the w8 keys count the
+// fp8-code GEMMs, the w4 keys the int4-code GEMMs).
 pybind11::dict moe_launch_counts(bool reset) {
   pybind11::dict d;
   auto put = [&](const std::string& key, std::atomic<int64_t>& c) {
@@ -743,6 +1070,8 @@ pybind11::dict moe_launch_counts(bool reset) {
     put(std::string("down_bm") + (b ? "128" : "32"), g_gemm[b][1]);
     put(std::string("gate_up_w8_bm") + (b ? "128" : "32"), g_gemm_w8[b][0]);
     put(std::string("down_w8_bm") + (b ? "128" : "32"), g_gemm_w8[b][1]);
+    put(std::string("gate_up_w4_bm") + (b ? "128" : "32"), g_gemm_w4[b][0]);
+    put(std::string("down_w4_bm") + (b ? "128" : "32"), g_gemm_w4[b][1]);
   }
   put("combine", g_combine);
   return d;

@@ -296,12 +296,15 @@ void mx4_launch_counts(pybind11::dict& d, bool reset);   // adds its keys to the
 // ---------------------------------------------------------------------------- moe.hip
 // Sparse mixture-of-experts MLP: router_w [E, H], gate_up_w [E, 2F, H], down_w [E, H, F], all bf16;
 // topk_ids int32 / topk_w f32 [T, k].  With gate_up_s f32 [E, 2F] and down_s f32 [E, H] the two expert
-// stacks are float8_e4m3fn codes with one scale per (expert, output row).
+// stacks are float8_e4m3fn codes with one scale per (expert, output row).  With gate_up_z / down_z as well
+// they are packed int4 codes uint8 [E, 2F, H / 2] / [E, H, F / 2] with f32 scales and uint8 zero points
+// [E, rows, K / G] per group of G input columns (the format of gemm_w4.hip per expert).
 bool moe_supported(int64_t H, int64_t F, int64_t E, int64_t k);
 void moe_route(at::Tensor ids, at::Tensor wts, at::Tensor x, at::Tensor router_w, bool norm_topk);
 void moe_experts(at::Tensor out, at::Tensor x, at::Tensor gate_up_w, at::Tensor down_w, at::Tensor ids,
                  at::Tensor wts, int64_t tile_rows_force, c10::optional<at::Tensor> gate_up_s,
-                 c10::optional<at::Tensor> down_s);
+                 c10::optional<at::Tensor> down_s, c10::optional<at::Tensor> gate_up_z,
+                 c10::optional<at::Tensor> down_z);
 pybind11::dict moe_launch_counts(bool reset);
 
 // -------------------------------------------------------------------------- runner.hip

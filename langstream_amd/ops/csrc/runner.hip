@@ -112,7 +112,9 @@ class LlamaRunner {
               c10::optional<std::vector<at::Tensor>> experts_gate_up_w = c10::nullopt,
               c10::optional<std::vector<at::Tensor>> experts_down_w = c10::nullopt, int64_t experts_per_token = 0,
               bool norm_topk = false, c10::optional<std::vector<at::Tensor>> experts_gate_up_s = c10::nullopt,
-              c10::optional<std::vector<at::Tensor>> experts_down_s = c10::nullopt, bool weights_mxfp4 = false)
+              c10::optional<std::vector<at::Tensor>> experts_down_s = c10::nullopt, bool weights_mxfp4 = false,
+              c10::optional<std::vector<at::Tensor>> experts_gate_up_z = c10::nullopt,
+              c10::optional<std::vector<at::Tensor>> experts_down_z = c10::nullopt)
       : embed_(embed), qkv_w_(qkv_w), o_w_(o_w), gate_up_w_(gate_up_w), down_w_(down_w), in_norm_(in_norm),
         post_norm_(post_norm), final_norm_(final_norm), lm_head_(lm_head), kc_(k_caches), vc_(v_caches),
         cos_sin_(cos_sin), hq_(hq), hkv_(hkv), d_(head_dim), eps_(eps), scale_(scale), vocab_(vocab_size),
@@ -136,7 +138,15 @@ class LlamaRunner {
       const bool ds = experts_down_s.has_value() && !experts_down_s->empty();
       TORCH_CHECK(gs == ds, "LlamaRunner: experts_gate_up_s and experts_down_s are given together or not at all");
       TORCH_CHECK(!gs || moe_, "LlamaRunner: experts_gate_up_s / experts_down_s without the expert weight lists");
-      xw8_ = gs;
+      // int4 experts (moe_gemm_w4): with the two per-layer lists of uint8 zero points as well (together or
+      // not at all, they need the scale lists) the expert stacks are packed int4 codes [E, rows, K / 2] and
+      // scales and zero points are [E, rows, K / G]
+      const bool gz = experts_gate_up_z.has_value() && !experts_gate_up_z->empty();
+      const bool dz = experts_down_z.has_value() && !experts_down_z->empty();
+      TORCH_CHECK(gz == dz, "LlamaRunner: experts_gate_up_z and experts_down_z are given together or not at all");
+      TORCH_CHECK(!gz || gs, "LlamaRunner: experts_gate_up_z / experts_down_z need experts_gate_up_s / experts_down_s");
+      xw4_ = gz;
+      xw8_ = gs && !gz;
     }
     if (moe_) {
       router_w_ = *router_w;
@@ -150,11 +160,13 @@ class LlamaRunner {
                   "LlamaRunner: one router and one pair of expert weight stacks per layer");
       for (size_t l = 0; l < L; ++l) {
         const at::Tensor &r = router_w_[l], &g = xgate_up_w_[l], &d = xdown_w_[l];
+        const int64_t pk = xw4_ ? 2 : 1;   // codes per byte of the last dimension
         TORCH_CHECK(r.dim() == 2 && g.dim() == 3 && d.dim() == 3 && g.size(0) == r.size(0) && d.size(0) == r.size(0) &&
-                        g.size(2) == r.size(1) && d.size(1) == r.size(1) && g.size(1) == 2 * d.size(2),
-                    "LlamaRunner: layers.", l, " expert weights are not router [E, H], gate_up [E, 2F, H], down [E, H, F]");
-        TORCH_CHECK(moe_supported(r.size(1), d.size(2), r.size(0), moe_k_), "LlamaRunner: layers.", l,
-                    " mixture of experts with H = ", r.size(1), ", F = ", d.size(2), ", E = ", r.size(0), ", k = ", moe_k_,
+                        pk * g.size(2) == r.size(1) && d.size(1) == r.size(1) && g.size(1) == 2 * pk * d.size(2),
+                    "LlamaRunner: layers.", l, " expert weights are not router [E, H], gate_up [E, 2F, H], down [E, H, F]",
+                    xw4_ ? " (int4: two codes per byte along the last dimension)" : "");
+        TORCH_CHECK(moe_supported(r.size(1), pk * d.size(2), r.size(0), moe_k_), "LlamaRunner: layers.", l,
+                    " mixture of experts with H = ", r.size(1), ", F = ", pk * d.size(2), ", E = ", r.size(0), ", k = ", moe_k_,
                     " is outside the MoE shape rule (H % 64 == 0, F % 64 == 0, E <= 256, 1 <= k <= min(E, 16))");
         const bool codes[2] = {g.scalar_type() == at::kFloat8_e4m3fn, d.scalar_type() == at::kFloat8_e4m3fn};
         const char* wn[2] = {"experts_gate_up", "experts_down"};
@@ -162,6 +174,38 @@ class LlamaRunner {
           TORCH_CHECK(codes[i] == xw8_, "LlamaRunner: layers.", l, ".", wn[i], "_w ",
                       xw8_ ? "must be float8_e4m3fn codes with expert scales"
                            : "holds float8_e4m3fn codes but no expert scales were given");
+        for (int i = 0; i < 2; ++i)
+          TORCH_CHECK(((i ? d : g).scalar_type() == at::kByte) == xw4_, "LlamaRunner: layers.", l, ".", wn[i], "_w ",
+                      xw4_ ? "must be uint8 int4 codes with expert scales and zero points"
+                           : "holds uint8 int4 codes but no expert scales and zero points were given");
+      }
+      if (xw4_) {
+        xgate_up_s_ = *experts_gate_up_s;
+        xdown_s_ = *experts_down_s;
+        xgate_up_z_ = *experts_gate_up_z;
+        xdown_z_ = *experts_down_z;
+        TORCH_CHECK(xgate_up_s_.size() == L && xdown_s_.size() == L && xgate_up_z_.size() == L && xdown_z_.size() == L,
+                    "LlamaRunner: one experts_gate_up_s, experts_down_s, experts_gate_up_z and experts_down_z per layer");
+        for (size_t l = 0; l < L; ++l) {
+          const at::Tensor* ss[2] = {&xgate_up_s_[l], &xdown_s_[l]};
+          const at::Tensor* zs[2] = {&xgate_up_z_[l], &xdown_z_[l]};
+          const at::Tensor* ws[2] = {&xgate_up_w_[l], &xdown_w_[l]};
+          const char* sn[2] = {"experts_gate_up", "experts_down"};
+          for (int i = 0; i < 2; ++i) {
+            const at::Tensor &s = *ss[i], &z = *zs[i], &w = *ws[i];
+            const int64_t K = 2 * w.size(2);
+            TORCH_CHECK(s.is_cuda() && s.device() == w.device() && s.scalar_type() == at::kFloat && s.is_contiguous() &&
+                            s.dim() == 3 && s.size(0) == w.size(0) && s.size(1) == w.size(1) && s.size(2) >= 1 &&
+                            K % s.size(2) == 0 && (K / s.size(2)) % 64 == 0,
+                        "LlamaRunner: layers.", l, ".", sn[i], "_s must be a contiguous float32 [", w.size(0), ", ",
+                        w.size(1), ", K / G] on the device of the weight, with a group size G that is a multiple of 64 "
+                        "and divides K = ", K);
+            TORCH_CHECK(z.is_cuda() && z.device() == w.device() && z.scalar_type() == at::kByte && z.is_contiguous() &&
+                            z.sizes() == s.sizes(),
+                        "LlamaRunner: layers.", l, ".", sn[i], "_z must be a contiguous uint8 tensor of the shape of ",
+                        sn[i], "_s on the device of the weight");
+          }
+        }
       }
       if (xw8_) {
         xgate_up_s_ = *experts_gate_up_s;
@@ -715,10 +759,15 @@ class LlamaRunner {
         at::Tensor tw = at::empty({T, moe_k_}, o.options().dtype(at::kFloat));
         moe_route(tid, tw, o, router_w_[l], moe_norm_);
         at::Tensor dn = at::empty_like(o);
-        if (xw8_)
-          moe_experts(dn, o, xgate_up_w_[l], xdown_w_[l], tid, tw, 0, xgate_up_s_[l], xdown_s_[l]);
+        if (xw4_)
+          moe_experts(dn, o, xgate_up_w_[l], xdown_w_[l], tid, tw, 0, xgate_up_s_[l], xdown_s_[l], xgate_up_z_[l],
+                      xdown_z_[l]);
+        else if (xw8_)
+          moe_experts(dn, o, xgate_up_w_[l], xdown_w_[l], tid, tw, 0, xgate_up_s_[l], xdown_s_[l], c10::nullopt,
+                      c10::nullopt);
         else
-          moe_experts(dn, o, xgate_up_w_[l], xdown_w_[l], tid, tw, 0, c10::nullopt, c10::nullopt);
+          moe_experts(dn, o, xgate_up_w_[l], xdown_w_[l], tid, tw, 0, c10::nullopt, c10::nullopt, c10::nullopt,
+                      c10::nullopt);
         all_reduce(dn);
         fused_add_rmsnorm(dn, residual, nxt, eps_);
         x = dn;
@@ -1046,6 +1095,8 @@ class LlamaRunner {
   std::vector<at::Tensor> router_w_, xgate_up_w_, xdown_w_;   // per-layer router and expert weight stacks, empty without
   std::vector<at::Tensor> xgate_up_s_, xdown_s_;   // fp8 experts: f32 scales [E, 2F] / [E, H] per layer, empty without
   bool xw8_ = false;           // the expert stacks are float8_e4m3fn codes with those scales
+  std::vector<at::Tensor> xgate_up_z_, xdown_z_;   // int4 experts: uint8 zero points per layer ([E, rows, K / G], as the scales then)
+  bool xw4_ = false;           // the expert stacks are packed int4 codes with group scales and zero points
   bool moe_ = false;           // every layer's MLP is a mixture of experts (moe.hip)
   int64_t moe_k_ = 0;          // experts per token
   bool moe_norm_ = false;      // the k routing weights are renormalised to sum 1
@@ -1685,7 +1736,8 @@ void bind_runners(py::module_& m) {
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
                     c10::optional<std::vector<at::Tensor>>, c10::optional<std::vector<at::Tensor>>,
                     c10::optional<std::vector<at::Tensor>>, int64_t, bool, c10::optional<std::vector<at::Tensor>>,
-                    c10::optional<std::vector<at::Tensor>>, bool>(),
+                    c10::optional<std::vector<at::Tensor>>, bool, c10::optional<std::vector<at::Tensor>>,
+                    c10::optional<std::vector<at::Tensor>>>(),
            py::arg("embed"), py::arg("qkv_w"), py::arg("o_w"), py::arg("gate_up_w"), py::arg("down_w"),
            py::arg("in_norm"), py::arg("post_norm"), py::arg("final_norm"), py::arg("lm_head"), py::arg("k_caches"),
            py::arg("v_caches"), py::arg("cos_sin"), py::arg("hq"), py::arg("hkv"), py::arg("head_dim"),
@@ -1699,7 +1751,8 @@ void bind_runners(py::module_& m) {
            py::arg("experts_gate_up_w") = py::none(), py::arg("experts_down_w") = py::none(),
            py::arg("experts_per_token") = 0, py::arg("norm_topk") = false,
            py::arg("experts_gate_up_s") = py::none(), py::arg("experts_down_s") = py::none(),
-           py::arg("weights_mxfp4") = false)
+           py::arg("weights_mxfp4") = false, py::arg("experts_gate_up_z") = py::none(),
+           py::arg("experts_down_z") = py::none())
       .def("forward", &LlamaRunner::forward, py::call_guard<py::gil_scoped_release>());
   py::class_<BertRunner>(m, "BertRunner")
       .def(py::init<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<std::vector<at::Tensor>>,

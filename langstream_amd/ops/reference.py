@@ -285,22 +285,32 @@ def moe_route(x, router_w, k: int, norm_topk: bool):
 
 
 def moe_mlp(x, router_w, gate_up_w, down_w, k: int, norm_topk: bool, route=None, slots: bool = False,
-            gate_up_s=None, down_s=None):
+            gate_up_s=None, down_s=None, gate_up_z=None, down_z=None):
     """out [T, H] in x's dtype; ``route`` = (topk_ids, topk_w) replaces the router.  With
     ``slots`` also the per-slot outputs y [T, k, H] (float64 values of x's dtype).  With the
     row scales ``gate_up_s`` [E, 2F] / ``down_s`` [E, H] the expert weights are fp8 codes and
-    stand for code * s, formed here in float64."""
+    stand for code * s, formed here in float64.  With the zero points ``gate_up_z`` / ``down_z``
+    as well they are packed int4 codes [E, rows, K / 2] with scales and zero points
+    [E, rows, K / G] and stand for s * (q - z) (dequantize_weight_int4 per expert, float64)."""
     if (gate_up_s is None) != (down_s is None):
         raise ValueError("moe_mlp: gate_up_s and down_s are given together or not at all")
+    if (gate_up_z is None) != (down_z is None):
+        raise ValueError("moe_mlp: gate_up_z and down_z are given together or not at all")
+    if gate_up_z is not None and gate_up_s is None:
+        raise ValueError("moe_mlp: the zero points gate_up_z / down_z need the scales gate_up_s / down_s")
     ids, w = route if route is not None else moe_route(x, router_w, k, norm_topk)
     T, H = x.shape
-    F = down_w.shape[2]
+    F = gate_up_w.shape[1] // 2
     xd = x.double()
     y = torch.zeros(T, ids.shape[1], H, dtype=torch.float64, device=x.device)
     for e in ids.unique().tolist():
         t, s = (ids == e).nonzero(as_tuple=True)
-        wgu, wdn = gate_up_w[e].double(), down_w[e].double()
-        if gate_up_s is not None:
+        if gate_up_z is not None:
+            wgu = dequantize_weight_int4(gate_up_w[e], gate_up_s[e], gate_up_z[e], torch.float64)
+            wdn = dequantize_weight_int4(down_w[e], down_s[e], down_z[e], torch.float64)
+        else:
+            wgu, wdn = gate_up_w[e].double(), down_w[e].double()
+        if gate_up_s is not None and gate_up_z is None:
             wgu, wdn = wgu * gate_up_s[e].double()[:, None], wdn * down_s[e].double()[:, None]
         gu = xd[t] @ wgu.t()
         act = (torch.nn.functional.silu(gu[:, :F]) * gu[:, F:]).to(x.dtype).double()

@@ -30,10 +30,11 @@ Configuration (``local-gpu-configuration`` resource):
   activations-dtype (bf16 | fp8; unset: the LS_ACTIVATIONS_DTYPE environment variable, else bf16.
   fp8 needs fp8 weights: steps of more than 4 rows quantise each projection's input rows to e4m3
   with one dynamic scale per row and run on the FP8 matrix instructions; never set by a checkpoint),
-  experts-dtype (bf16 | fp8; unset: the LS_EXPERTS_DTYPE environment variable, else bf16.
+  experts-dtype (bf16 | fp8 | int4; unset: the LS_EXPERTS_DTYPE environment variable, else bf16.
   fp8 on a mixture-of-experts model quantises the expert matrices of every layer at load, e4m3 codes
-  with one scale per expert and output row; every other tensor keeps its type; refused on a dense
-  model and together with fp8 weights or activations),
+  with one scale per expert and output row; int4 to 4-bit codes with a scale and a zero point per
+  expert, output row and group of 128 input columns; every other tensor keeps its type; refused on a
+  dense model and together with fp8 weights or activations),
   sliding-window (true | false; unset: the LS_SLIDING_WINDOW environment variable, else false.
   A model-path with an active sliding window, Mistral or Qwen2 with use_sliding_window: true
   serves every position with windowed attention in the layers that have a window, false only
@@ -207,8 +208,8 @@ class ServiceRegistry:
             if ad not in ("bf16", "fp8"):
                 raise ValueError(f"activations-dtype {ad!r}: expected bf16 or fp8")
             xd = str(c.get("experts-dtype") or os.environ.get("LS_EXPERTS_DTYPE") or "bf16").lower()
-            if xd not in ("bf16", "fp8"):
-                raise ValueError(f"experts-dtype {xd!r}: expected bf16 or fp8")
+            if xd not in ("bf16", "fp8", "int4"):
+                raise ValueError(f"experts-dtype {xd!r}: expected bf16, fp8 or int4")
             model_ = LlamaModel(mcfg, device=device, dtype=dtype, tp=self.tp, weights_dtype=wd, activations_dtype=ad,
                                 experts_dtype=xd)
             if sd is not None:

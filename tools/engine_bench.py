@@ -193,8 +193,9 @@ if __name__ == "__main__":
                          "int4: W4A16 kernels, quantised at load in groups of 128, mxfp4: W4A8 kernels, quantised at load)")
     ap.add_argument("--activations-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="LLM: fp8 (with --weights-dtype fp8) runs steps of more than 4 rows on the W8A8 kernels")
-    ap.add_argument("--experts-dtype", choices=("bf16", "fp8"), default="bf16",
-                    help="LLM: fp8 stores the expert matrices of a mixture-of-experts model as e4m3 codes (W8A16 grouped GEMMs)")
+    ap.add_argument("--experts-dtype", choices=("bf16", "fp8", "int4"), default="bf16",
+                    help="LLM: fp8 stores the expert matrices of a mixture-of-experts model as e4m3 codes (W8A16 grouped GEMMs), "
+                         "int4 as group-quantised 4-bit codes (W4A16 grouped GEMMs)")
     ap.add_argument("--qkv-bias", action="store_true",
                     help="LLM: the model's shape with a random bias on the QKV projection (LlamaConfig.qkv_bias)")
     ap.add_argument("--texts", type=int, default=2048)

@@ -1,8 +1,8 @@
 """One mixture-of-experts layer (ops/csrc/moe.hip: route, align, two grouped GEMMs, combine) with
-bf16 and with fp8 experts, alternated in one process over rotating weight copies larger than the
+bf16, fp8 and int4 experts, alternated in one process over rotating weight copies larger than the
 caches.  Prints one JSON line per (T, variant): median (min - max) us per call over the windows and
 the GB/s of the weights actually read (router, the three matrices of every expert that received a
-token, and their scales).
+token, and their scales and zero points).
 
   python tools/moe_bench.py --shape qwen3 --T 1 16 256 4096
   python tools/moe_bench.py --shape mixtral --T 16 --variants bf16 --so <another build's _hip_ops.so>
@@ -17,7 +17,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from langstream_amd import ops  # noqa: E402
-from langstream_amd.models.llama import quantize_experts_fp8  # noqa: E402
+from langstream_amd.models.llama import quantize_experts_fp8, quantize_experts_int4  # noqa: E402
 
 SHAPES = {"qwen3": (128, 8, 2048, 768, 4), "mixtral": (8, 2, 4096, 14336, 3)}   # E, k, H, F, weight copies
 
@@ -26,10 +26,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", choices=sorted(SHAPES), default="qwen3")
     ap.add_argument("--T", type=int, nargs="+", default=[1, 16, 256, 4096])
-    ap.add_argument("--variants", nargs="+", choices=("bf16", "fp8"), default=["bf16", "fp8"])
+    ap.add_argument("--variants", nargs="+", choices=("bf16", "fp8", "int4"), default=["bf16", "fp8", "int4"])
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--so", help="time another build of the extension (bf16 only before fp8 experts)")
+    ap.add_argument("--so", help="time another build of the extension (bf16 only before fp8 experts, no int4 before int4 experts)")
     args = ap.parse_args()
     if args.so:
         ops._SO = os.path.abspath(args.so)
@@ -46,6 +46,10 @@ def main():
     if "fp8" in args.variants:
         (gc, gs), (dc, ds) = quantize_experts_fp8(gu), quantize_experts_fp8(dn)
         sets["fp8"] = [(gc.clone(), dc.clone(), dict(gate_up_s=gs.clone(), down_s=ds.clone())) for _ in range(copies)]
+    if "int4" in args.variants:   # groups of 128 input columns: 0.5 B + 5 / 128 B per weight
+        (gc, gs, gz), (dc, ds, dz) = quantize_experts_int4(gu), quantize_experts_int4(dn)
+        sets["int4"] = [(gc.clone(), dc.clone(), dict(gate_up_s=gs.clone(), down_s=ds.clone(), gate_up_z=gz.clone(),
+                                                      down_z=dz.clone())) for _ in range(copies)]
     del gu, dn
 
     def call(x, out, ids, w, ws):
@@ -73,7 +77,8 @@ def main():
                 torch.cuda.synchronize()
                 times[v].append(a.elapsed_time(b) * 1e3 / args.calls)
         for v, ts in times.items():
-            wbytes = E * H * 2 + used * 3 * H * F * (2 if v == "bf16" else 1) + (used * (2 * F + H) * 4 if v == "fp8" else 0)
+            wbytes = E * H * 2 + {"bf16": used * 3 * H * F * 2, "fp8": used * (3 * H * F + (2 * F + H) * 4),
+                                  "int4": used * (3 * H * F // 2 + 3 * H * F // 128 * 5)}[v]
             med = statistics.median(ts)
             print(json.dumps({"shape": args.shape, "T": T, "variant": v, "experts_used": used, "weight_MB": round(wbytes / 1e6, 1), "us": round(med, 1),
                               "min_us": round(min(ts), 1), "max_us": round(max(ts), 1),
